@@ -12,7 +12,10 @@ embarrassingly: every rank renders its own stream of camera poses with a replica
 collectives are the timing barrier and the reduction of the counters.
 
 Prints ONE JSON line (rank 0).  `roofline` prices the render kernel against HBM with the algorithmic gather bytes
-(512 B per ray-sample); `cpu_baseline` is the CPU oracle (a port: the reference has no CPU path) on a bounded sample.
+(512 B per ray-sample).  A plain run does only what that line's headline needs: set-up, warm-up, the --steps timed steps.
+--full adds the secondary measurements and checks, each of which takes runs of its own: `cpu_baseline` (the CPU oracle, a port: the
+reference has no CPU path, on a bounded sample) with the PSNR against it, the `fitted` model and its `train` block, `multi_frame`,
+`drop_in` and `nav`.  --dump-outputs DIR writes the arrays the last timed step returned (`dump_outputs`).
 """
 import argparse
 import contextlib
@@ -86,6 +89,32 @@ def sources_sha16(files=FRAME_SOURCES):
     return h.hexdigest()[:16]
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_KEEP_WHOLE_BYTES = 1 << 20
+
+
+def dump_outputs(outputs, dst, seed=0):
+    """--dump-outputs: one DST/<name>.npy per array of `outputs` (float32; integer arrays as float64, which holds every int32 exactly), so that
+    two builds run with the same arguments can be compared output for output.  Above 64 MB in all, every array larger than 1 MB is cut to a
+    fixed, seeded sample of its flattened elements (the same indices on every run of the same shapes)."""
+    os.makedirs(dst, exist_ok=True)
+    arrays = {}
+    for name, t in outputs.items():
+        a = t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+        arrays[name] = a.astype(np.float32 if np.issubdtype(a.dtype, np.floating) else np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        large = [k for k, a in arrays.items() if a.nbytes > DUMP_KEEP_WHOLE_BYTES]
+        room = DUMP_LIMIT_BYTES - sum(a.nbytes for k, a in arrays.items() if k not in large)
+        frac = room / sum(arrays[k].nbytes for k in large)
+        for k in large:
+            flat = arrays[k].reshape(-1)
+            idx = np.sort(np.random.default_rng(seed).choice(flat.size, int(flat.size * frac), replace=False))
+            arrays[k] = flat[idx]
+    for name, a in arrays.items():
+        np.save(os.path.join(dst, name + ".npy"), a)
+
+
 def committed_counters(pattern, files):
     """per-dispatch PMC means of the newest committed profile matching `pattern`, or (None, reason) when it was collected for other sources"""
     import csv
@@ -140,6 +169,7 @@ def bench_train(args, rank, world, dev, W, teacher):
         return float(student.step_counter[:n, 0].float().mean().item()) if n else float(student.mean_count)
 
     host_ms = [None]                                                       # ms per step the host needed to queue the last timed phase
+    last_loss = [None]                                                     # what the last timed step returned (--dump-outputs)
 
     def timed_phase(first, count):
         ngp_hip.TIMERS = {}
@@ -154,6 +184,7 @@ def bench_train(args, rank, world, dev, W, teacher):
         scatter_ms, calls = ngp_hip.timer_ms("grid_encode_backward")
         ngp_hip.TIMERS = None
         host_ms[0] = queued / count * 1e3
+        last_loss[0] = loss
         return elapsed, float(loss), points_now(), scatter_ms, calls
 
     k0 = 0
@@ -168,6 +199,9 @@ def bench_train(args, rank, world, dev, W, teacher):
     elapsed, loss, points, scatter_ms, calls = timed_phase(k0, args.steps)  # steady state
     rays_all, t_max = sharding.reduce_throughput(n_rays * args.steps, elapsed, dev)
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs({"loss": last_loss[0]}, args.dump_outputs)
+
         def roof(pts, ms, profiled_phase=False):
             """the table-gradient scatter (binned: k_gs_bin + k_gs_accumulate, event-timed together): 512 algorithmic bytes of contributions per
             point against HBM (no atomics left: the bound is the entry traffic), with the float-atomic peak the replaced kernel was priced at beside it"""
@@ -524,6 +558,10 @@ def main():
     ap.add_argument("--no-nav-block", action="store_true")
     ap.add_argument("--drop-in-frames", type=int, default=5, help="`drop_in` block: timed 800x800 frames of the unchanged-caller loop")
     ap.add_argument("--no-drop-in-block", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements and checks (cpu_baseline and the PSNR against the CPU oracle, fitted / train, multi_frame, "
+                         "drop_in, nav; the --no-* options above leave out single ones); without it a run does only what the headline needs")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the arrays the last timed step returned to DIR/<name>.npy (float32 / float64, 64 MB at most)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -660,6 +698,8 @@ def main():
         if use_dist:
             dist.destroy_process_group()
         return
+    if args.dump_outputs:
+        dump_outputs({k: v for k, v in out.items() if torch.is_tensor(v)}, args.dump_outputs)
 
     value = samples_all / elapsed_max
     ms_per_step = 1e3 * elapsed_max / args.steps
@@ -749,7 +789,7 @@ def main():
         else:
             result["roofline"]["traffic_stale"] = info
 
-    if args.path == "fused" and world == 1 and not strong and args.frames_per_launch > 1 and H % 8 == 0 and Wd % 8 == 0:
+    if args.full and args.path == "fused" and world == 1 and not strong and args.frames_per_launch > 1 and H % 8 == 0 and Wd % 8 == 0:
         # secondary: P poses per launch (ngp_render_frames_camera): the same pixels; ramp and drain of the persistent kernel paid once per P frames.
         # The headline `value` stays one frame per launch (BASELINE's metric: a viewer renders the frame it needs now).
         P_ = args.frames_per_launch
@@ -778,15 +818,15 @@ def main():
                                               "kernel": "k_render_frame_multi", "avg_launch_ms": 1e3 * k_s}}
     if fit is not None:
         result["fit"] = fit
-    if args.model == "handset" and args.path == "fused" and world == 1 and not strong and not args.no_fit:
+    if args.full and args.model == "handset" and args.path == "fused" and world == 1 and not strong and not args.no_fit:
         result["fitted"] = fitted_block(args, dev, W, ren, rays, Wd)
         result["train"] = result["fitted"].pop("train")      # config 3's steady state = the last steps of that fit, timed (None with --no-train-block)
-    default_line = args.model == "handset" and args.path == "fused" and world == 1 and not strong
+    default_line = args.full and args.model == "handset" and args.path == "fused" and world == 1 and not strong
     if default_line and not args.no_drop_in_block:
         result["drop_in"] = drop_in_block(args, ren, rays, N)
     if default_line and not args.no_nav_block and args.workload == "ring":
         result["nav"] = nav_block(args, dev, W)
-    if not args.no_cpu and world == 1:
+    if args.full and not args.no_cpu and world == 1:
         from oracle import ngp_oracle as O, render_oracle as R
         O.build()
         # a one-GPU box grants this process a share of the host (16 cores' worth on the pool this was measured on) whatever the affinity mask says:

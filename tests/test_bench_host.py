@@ -85,3 +85,21 @@ def test_bare_multi_gpu_command_fails_when_a_rank_does(monkeypatch, capsys):
     with pytest.raises(SystemExit) as e:
         bench.main()
     assert e.value.code == 3 and capsys.readouterr().out == ""
+
+
+def test_dump_outputs_writes_float_arrays_and_caps_the_total(tmp_path):
+    """--dump-outputs: float arrays as float32, integer counters as float64 (exact); above 64 MB the large arrays are cut to a seeded sample
+    that is the same on every run"""
+    small = {"image": torch.rand(2, 5, 3, dtype=torch.float16), "stats": torch.tensor([7, 1 << 30, -2, 0], dtype=torch.int32)}
+    bench.dump_outputs(small, str(tmp_path / "a"))
+    img, st = np.load(tmp_path / "a" / "image.npy"), np.load(tmp_path / "a" / "stats.npy")
+    assert img.dtype == np.float32 and img.shape == (2, 5, 3) and np.array_equal(img, small["image"].float().numpy())
+    assert st.dtype == np.float64 and st.tolist() == [7, 1 << 30, -2, 0]
+    big = {"image": torch.arange(12 << 20, dtype=torch.float32).view(-1, 3), "depth": torch.zeros(6 << 20), "stats": small["stats"]}
+    for d in ("b", "c"):
+        bench.dump_outputs(big, str(tmp_path / d))
+    sizes = {f.name: f.stat().st_size for f in (tmp_path / "b").iterdir()}
+    assert sum(sizes.values()) <= bench.DUMP_LIMIT_BYTES + 3 * 128 and set(sizes) == {"image.npy", "depth.npy", "stats.npy"}
+    a, b = np.load(tmp_path / "b" / "image.npy"), np.load(tmp_path / "c" / "image.npy")
+    assert np.array_equal(a, b) and a.size > (8 << 20) and np.all(np.diff(a) > 0)       # same sample twice, of distinct elements in order
+    assert np.load(tmp_path / "b" / "stats.npy").tolist() == [7, 1 << 30, -2, 0]       # small arrays are kept whole

@@ -11,7 +11,7 @@ TAG=${1:-r01}; shift
 MODE=full
 if [ "${1:-}" = "short" ] || [ "${1:-}" = "full" ]; then MODE=$1; shift; fi
 if [ "${1:-}" = "--" ]; then shift; fi
-if [ $# -eq 0 ]; then set -- bench.py --steps 30 --warmup 5 --no-cpu; fi
+if [ $# -eq 0 ]; then set -- bench.py --steps 30 --warmup 5 --no-cpu --full; fi
 export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 SCRIPT=$R/$1; shift
