@@ -533,6 +533,30 @@ int ngp_render_frames_camera(const ngp_field_t* field, const float* poses_host, 
                              float* image, float* depth, float* weights_sum, uint32_t* stats,
                              void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------ */
+/* Mesh extraction  (reference: nerf/utils.py:150-182, 533-555 run PyMCubes   */
+/* on the host; csrc/mesh.hip)                              */
+/* ------------------------------------------------------------------------ */
+
+/* Marching cubes over a float32 lattice u[X][Y][Z] (device, C order), 2 <= X, Y, Z <= 1024.  A corner is inside iff
+ * u > threshold.  One vertex per crossing lattice edge, ordered by edge id 3 * ((x*Y + y)*Z + z) + a, float32 [V,3] in
+ * INDEX space; int32 triangles [T,3], cells in increasing linear index, normals (right-hand rule) from inside to outside;
+ * crack-free: ambiguous faces separate their inside corners.  Deterministic, bit-identical from run to run.
+ * Two calls on one workspace of ngp_marching_cubes_workspace bytes, the same u and threshold:
+ *   ngp_marching_cubes_count writes V and T to the host pointers.  It is the ONE entry point of this library that
+ *     synchronises (it reads the two totals back: once per extraction); NGP_EINVAL when V >= 2^31.
+ *   ngp_marching_cubes_emit writes vertices [V,3] and triangles [T,3] (V, T as count returned: no write reaches past them).
+ * The workspace is 0 for sizes out of range. */
+#define NGP_MC_MAX_TRIS 5
+#define NGP_MC_TABLE_ROW (3 + 3 * NGP_MC_MAX_TRIS)   /* bytes per case: edge mask (low, high byte), triangle count, local edges (255 = unused) */
+size_t ngp_marching_cubes_workspace(uint32_t X, uint32_t Y, uint32_t Z);
+int ngp_marching_cubes_count(const float* u, uint32_t X, uint32_t Y, uint32_t Z, float threshold, void* workspace, size_t workspace_bytes,
+                             uint64_t* V_host, uint64_t* T_host, void* stream);
+int ngp_marching_cubes_emit(const float* u, uint32_t X, uint32_t Y, uint32_t Z, float threshold, const void* workspace, size_t workspace_bytes,
+                            float* vertices, uint64_t V, int32_t* triangles, uint64_t T, void* stream);
+/* The 256-case table (256 rows of NGP_MC_TABLE_ROW bytes) copied to a host buffer; touches no device. */
+int ngp_marching_cubes_table(uint8_t* table_host, size_t bytes);
+
 #ifdef __cplusplus
 }
 #endif

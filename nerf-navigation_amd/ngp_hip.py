@@ -118,6 +118,10 @@ _SIGNATURES = {
     "ngp_render_frames_workspace": (c_sz, [c_u32, c_u32]),
     "ngp_render_frames_camera": (c_int, [c_vp, c_vp, c_u32, c_vp, c_u32, c_u32, c_vp, c_f32, c_vp, c_u32, c_u32, c_f32, c_u32, c_vp,
                                          c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "ngp_marching_cubes_workspace": (c_sz, [c_u32, c_u32, c_u32]),
+    "ngp_marching_cubes_count": (c_int, [c_vp, c_u32, c_u32, c_u32, c_f32, c_vp, c_sz, c_vp, c_vp, c_vp]),
+    "ngp_marching_cubes_emit": (c_int, [c_vp, c_u32, c_u32, c_u32, c_f32, c_vp, c_sz, c_vp, c_u64, c_vp, c_u64, c_vp]),
+    "ngp_marching_cubes_table": (c_int, [c_vp, c_sz]),
 }
 
 EXPORTS = tuple(_SIGNATURES)
