@@ -5,13 +5,6 @@
 #include "ngp_mlp.h"
 #include "ngp_sh.h"
 
-#ifndef RF_MIX_BLEND
-#define RF_MIX_BLEND 2                 // products of the trilinear blend, half(w * float(v)) with TWO roundings as in the reference:
-                                       //   0: cvt / v_pk_mul_f32 / cvt (ngp_f2h)                                          4.02-4.04 ms
-                                       //   2: v_fma_mix_f32 (binary32 product straight from the packed halves) + one cvt_pk: same bits, 3.87-3.88 ms
-                                       //   1: v_fma_mixlo/hi_f16 -- timing only, NOT the reference arithmetic: it rounds the exact product
-                                       //      once (1,637 of the 1.92 M values of an 800x800 image differ by up to 7.5e-5)  3.95-3.97 ms
-#endif
 static constexpr int RF_L = 16;       // levels (4 per lane group)
 static constexpr uint32_t RF_BLOCK = 256;
 // workgroups of k_field_forward_lds per CU.  Two 16-point tiles per pass need ~200 VGPRs: at 4 workgroups per CU (4 waves per SIMD,
@@ -119,19 +112,9 @@ __device__ __forceinline__ rf_row2 rf_rows(const rf_params& P, uint32_t byte_off
 // INRANGE: the caller guarantees |w| <= bound (march samples are clamped to the box, raymarching.cu:365-367), so the
 // normalised position is in [0,1] and the out-of-range handling is dead code.
 // The gathers of one PAIR of iterations (h = 0: levels g and 4+g, h = 1: levels 8+g and 12+g) for a normalised position:
-// cell, fractions, byte offsets, loads issued (nothing waits here).  Splitting the encoder in pairs lets the frame kernel
-// issue the next tile's pair 1 (the hashed levels, the slow gathers) before the current tile's MLP (RV_PIPELINE).
+// cell, fractions, byte offsets, loads issued (nothing waits here); rf_encode issues both pairs before it blends either.
+// (Paired x-corner loads on hashed levels were measured and not adopted: profiles/HISTORY.md 4.1.)
 struct rf_pair { uint32_t raw[2][8]; float fx[2], fy[2], fz[2]; };
-
-#ifndef RF_PAIR_HASHED
-#define RF_PAIR_HASHED 0               // 1: on hashed levels an even-x lane fetches both x-corners with ONE aligned 8-byte load; A/B: HISTORY 4
-#endif
-__device__ __forceinline__ rf_row2 rf_rows8(const rf_params& P, uint32_t byte_off) {      // one 8-byte load, 8-byte aligned
-    asm("" : "+v"(byte_off));
-    typedef uint32_t u2 __attribute__((ext_vector_type(2)));
-    const u2 v = *reinterpret_cast<const u2*>(reinterpret_cast<const char*>(P.table) + byte_off);
-    return rf_row2{v.x, v.y};
-}
 
 __device__ __forceinline__ void rf_normalise(const rf_params& P, float wx, float wy, float wz, float& x0, float& x1, float& x2) {
     // GridEncoder.forward (grid.py:144): (x + bound) / (2 bound) -- as torch evaluates it on the GPU: a tensor divided by a host scalar is the
@@ -161,17 +144,7 @@ __device__ __forceinline__ void rf_gather_pair(const rf_params& P, const rf_lane
             // x + y*s1 + z*s2 (always < size); the x-neighbour is the next row: one 8-byte load per (y, z)
             const uint32_t o00 = __umul24(gz, lv.s2b[i]) + (__umul24(gy, lv.s1b[i]) + ((gx << 2) + lv.base4[i]));
             const uint32_t o01 = o00 + lv.s1b[i], o10 = o00 + lv.s2b[i], o11 = o01 + lv.s2b[i];
-#ifdef RV_EXPERIMENT_FREE_LEVELS   // timing-only build (wrong image): the gathers of levels 0 .. RV_EXPERIMENT_FREE_LEVELS-1 are not issued at all --
-            // an upper bound on what serving those levels from LDS could gain (an LDS read cannot be cheaper than no read)
-            // (level 0 keeps its constant-one second feature, which the bench model's density logit reads: same densities, same sample count)
-            const uint32_t cst = ((threadIdx.x & 63u) >> 4) == 0u ? 0x3C000000u : 0u;
-            rf_row2 r0 = {cst, cst}, r1 = {cst, cst}, r2 = {cst, cst}, r3 = {cst, cst};
-            if (i != 0 || (int)((threadIdx.x & 63u) >> 4) >= RV_EXPERIMENT_FREE_LEVELS) {
-                r0 = rf_rows(P, o00); r1 = rf_rows(P, o01); r2 = rf_rows(P, o10); r3 = rf_rows(P, o11);
-            }
-#else
             const rf_row2 r0 = rf_rows(P, o00), r1 = rf_rows(P, o01), r2 = rf_rows(P, o10), r3 = rf_rows(P, o11);
-#endif
             raw[i & 1][0] = r0.lo; raw[i & 1][1] = r0.hi; raw[i & 1][2] = r1.lo; raw[i & 1][3] = r1.hi;
             raw[i & 1][4] = r2.lo; raw[i & 1][5] = r2.hi; raw[i & 1][6] = r3.lo; raw[i & 1][7] = r3.hi;
         } else {
@@ -182,38 +155,8 @@ __device__ __forceinline__ void rf_gather_pair(const rf_params& P, const rf_lane
                 const uint32_t hy1 = hy + (P1 << 2), hz1 = hz + (P2 << 2);
                 const uint32_t a0 = (gx << 2) & m, a1 = ((gx << 2) + 4u) & m;
                 const uint32_t yz0 = (hy ^ hz) & m, yz1 = (hy1 ^ hz) & m, yz2 = (hy ^ hz1) & m, yz3 = (hy1 ^ hz1) & m;
-#if RF_PAIR_HASHED
-                // The x-neighbour of a hashed corner: fast_hash xors x * 1 into the index (gridencoder.cu:35-51), so for an EVEN cell coordinate
-                // index(x + 1, y, z) = index(x, y, z) ^ 1 (2^k rows, k >= 1: the mask keeps bit 0): both rows lie in one aligned 8-byte word and ONE
-                // load serves both corners -- which half is which depends on bit 0 of the (y, z) hash.  Lanes with an odd x fetch their second
-                // corner with a load of their own, the even lanes masked off: the texture path is busy per lane address (HISTORY 1), and these
-                // levels go from 8 to 6 of them per sample on average.  Same rows, same bits.
-                {
-                    const uint32_t yz[4] = {yz0, yz1, yz2, yz3};
-                    const bool odd = (gx & 1u) != 0u;
-                    #pragma unroll
-                    for (int k = 0; k < 4; k++) {
-                        const uint32_t A = a0 ^ yz[k];                                 // byte offset of corner (x, y, z) inside the level
-                        const rf_row2 r = rf_rows8(P, (A & ~4u) + b);
-                        const bool hi = (A & 4u) != 0u;
-                        raw[i & 1][2 * k] = hi ? r.hi : r.lo;
-                        raw[i & 1][2 * k + 1] = hi ? r.lo : r.hi;                      // row A ^ 4: corner (x + 1, y, z) when x is even
-                    }
-                    if (odd) {
-                        #pragma unroll
-                        for (int k = 0; k < 4; k++) raw[i & 1][2 * k + 1] = rf_row(P, (a1 ^ yz[k]) + b);
-                    }
-                    continue;
-                }
-#endif
                 off[0] = (a0 ^ yz0) + b; off[1] = (a1 ^ yz0) + b; off[2] = (a0 ^ yz1) + b; off[3] = (a1 ^ yz1) + b;
                 off[4] = (a0 ^ yz2) + b; off[5] = (a1 ^ yz2) + b; off[6] = (a0 ^ yz3) + b; off[7] = (a1 ^ yz3) + b;
-#ifdef RV_EXPERIMENT_WINDOW        // timing-only build: levels 8..15 gather inside a window of this many bytes per level
-                if (i >= 2) {
-                    #pragma unroll
-                    for (int c = 0; c < 8; c++) off[c] = b + ((off[c] - b) & (uint32_t)(RV_EXPERIMENT_WINDOW - 1));
-                }
-#endif
             } else if (cls.select & bit) {
                 // both kinds in one wave: compute both offsets, select per lane, no branch
                 const bool dense = lv.s1b[i] != 0u;
@@ -253,8 +196,8 @@ __device__ __forceinline__ void rf_gather_pair(const rf_params& P, const rf_lane
 //   w = (wx * wy) * wz in binary32;  results[ch] += w * grid[...]  ==  half(float(result) + float(half(w * float(v))))
 // The product is rounded to binary32 (v_fma_mix_f32: fma32(w, float(v), +0) reads the half straight out of the packed row)
 // and then to binary16 by the packed conversion; the +0 addend only turns a -0 product into +0, which a sum that starts at
-// +0 cannot tell apart.  v_fma_mixlo/mixhi_f16 would do both steps in one instruction but round only once (RF_MIX_BLEND 1,
-// timing only).  The packed-half add is the correctly rounded binary16 sum.
+// +0 cannot tell apart.  v_fma_mixlo/mixhi_f16 would do both steps in one instruction but round only once, which is not the
+// reference's arithmetic.  The packed-half add is the correctly rounded binary16 sum.
 __device__ __forceinline__ void rf_blend_pair(const rf_pair& in, int h, ngp_h8& out) {
     typedef float f2 __attribute__((ext_vector_type(2)));
     typedef _Float16 h2 __attribute__((ext_vector_type(2)));
@@ -268,24 +211,13 @@ __device__ __forceinline__ void rf_blend_pair(const rf_pair& in, int h, ngp_h8& 
         #pragma unroll
         for (int c = 0; c < 8; c++) {
             const float wc = w[c >> 1][c & 1];
-#if RF_MIX_BLEND == 1
-            uint32_t prod;
-            asm("v_fma_mixlo_f16 %0, %1, %2, 0 op_sel_hi:[0,1,0]" : "=v"(prod) : "v"(wc), "v"(in.raw[j][c]));
-            asm("v_fma_mixhi_f16 %0, %1, %2, 0 op_sel:[0,1,0] op_sel_hi:[0,1,0]" : "+v"(prod) : "v"(wc), "v"(in.raw[j][c]));
-            acc = acc + __builtin_bit_cast(h2, prod);
-#elif RF_MIX_BLEND == 2
             // binary32 products straight from the packed halves (v_fma_mix_f32 = fma32(w, float(v), +0), rounded to binary32),
-            // then ONE packed conversion: the reference's two roundings in 3 instructions instead of 5
+            // then ONE packed conversion: the reference's two roundings in 3 instructions instead of 5 (ms per frame: DESIGN.md 3.2)
             float p0, p1;
             asm("v_fma_mix_f32 %0, %1, %2, 0 op_sel_hi:[0,1,0]" : "=v"(p0) : "v"(wc), "v"(in.raw[j][c]));
             asm("v_fma_mix_f32 %0, %1, %2, 0 op_sel:[0,1,0] op_sel_hi:[0,1,0]" : "=v"(p1) : "v"(wc), "v"(in.raw[j][c]));
             const h2 prod = {(_Float16)p0, (_Float16)p1};
             acc = acc + prod;
-#else
-            const h2 v = __builtin_bit_cast(h2, in.raw[j][c]);
-            const h2 prod = {ngp_f2h(wc * (float)v.x), ngp_f2h(wc * (float)v.y)};
-            acc = acc + prod;
-#endif
         }
         out[4 * h + 2 * j] = acc.x;
         out[4 * h + 2 * j + 1] = acc.y;

@@ -81,14 +81,9 @@ extern "C" int ngp_field_forward_half(const ngp_field_t* field_host, const float
 // holds, and LDS bounds that: 1024 threads x 5 samples 4.33 | 768 x 7 4.24 | 512 x 12 (2 waves/SIMD, 256 VGPRs, no scratch;
 // march budget 512) 4.05 | 512 x 10 4.57 | 512 x 8 4.25.
 #ifndef RV_S
-#define RV_S 12                        // samples each lane may march per round (k_render_frame_multi); 1 = k_render_frame
+#define RV_S 12                        // samples each lane may march per round (k_render_frame_multi)
 #endif
-#ifndef RV_SORT_COLUMNS
-#define RV_SORT_COLUMNS 1      // 1: tile columns taken in order of decreasing sample count (fewer dummy columns), 0: lane order
-#endif
-#ifndef RV_XCD_QUEUES
-#define RV_XCD_QUEUES 1        // 1: eight ray queues, one per XCD (image bands), with stealing; 0: one global queue
-#endif
+static_assert(RV_S >= 2, "RV_S must be at least 2: the one-sample-per-round frame kernel has been removed");
 // Coherence knobs (round 2; same images, tools/ab_variants.sh and tools/ab_trained.sh: ms per 800x800 frame of the hand-set model | G ray-samples/s on
 // a model fitted for 2,000 and for 8,000 steps).  Lane l of a wave gathers for the samples of ray l; what the 64 addresses of one gather instruction
 // share (cells of the coarse and middle levels, i.e. cache lines) decides how fast a CU's texture path and L1 turn a tile around.
@@ -108,41 +103,19 @@ extern "C" int ngp_field_forward_half(const ngp_field_t* field_host, const float
                                // 0 (off): 3.49 | 5.3, 5.3    8: 3.53 | 8.1, 6.7    12: 3.51 | 7.8    16: 3.46 | 8.1, 6.9    24: 3.45 | 7.7, 6.6    32: 3.46 | 7.3, 6.5    48: 3.49 | 6.7
                                // (limiting every lane to (smallest t of the wave) + 24 steps instead -- the laggard crawls through its empty space 24 steps a
                                //  round -- gave 7.4-7.7 on the fitted model but 4.06 ms on the hand-set one: rounds of 87 samples instead of 636)
-#ifndef RV_CU_CHUNKS
-#define RV_CU_CHUNKS 0         // 1: the waves of a workgroup (= one CU) draw their 8x8 tiles from a CU-LOCAL chunk of 8 tiles = a block of 4 x 2 adjacent tiles
-#endif                         // (32 x 16 pixels), fetched from the band queue with one atomic: neighbouring tiles share an L1.  A/B on MI355X: see DESIGN 3.2.
 #ifndef RV_BLOCK_THREADS
 #define RV_BLOCK_THREADS 512
 #endif
 #ifndef RV_BLOCKS_PER_CU
-#define RV_BLOCKS_PER_CU (RV_S > 1 ? 1 : 2)   // the sample slots (96 KiB at 512 x 12) only fit beside ONE copy of the weights per CU
+#define RV_BLOCKS_PER_CU 1             // the sample slots (96 KiB at 512 x 12) only fit beside ONE copy of the weights per CU
 #endif
-#ifndef RV_TILE_PAIRS
-#define RV_TILE_PAIRS 1                // evaluate tiles k and k+1 of a lane group together: two MFMA chains per pass
-#endif
-#ifndef RV_PIPELINE
-#define RV_PIPELINE 0                  // 1: issue the next tile's gathers before the current tile's MLP (software pipeline across
-#endif                                 // tiles).  A/B on MI355X: at 4 waves/SIMD (hashed half prefetched) 5.0-5.2 vs 4.8-5.0 ms; at
-                                       // 2 waves/SIMD (whole tile prefetched, 208 VGPRs) 4.17-4.30 vs 4.12-4.36 ms: the frame is bound
-                                       // by VALU throughput, not by the latency a prefetch would hide.  Off.
-#ifndef RV_TILE_ORDER
-#define RV_TILE_ORDER 0                // 1: hand out the 8x8 pixel tiles most expensive first (k_tile_estimate / k_tile_order).
-#endif                                 // A/B on MI355X: 5.25-5.35 ms with, 5.0-5.2 ms without: the frame is bound by L1 tag and
-                                       // VALU throughput, not by its tail, and sorted tiles lose spatial locality.  Kept for scenes
-                                       // with a heavier tail; off by default.
-#ifndef RV_BLOCK_SKIP
-#define RV_BLOCK_SKIP 1                // verified skips through empty 4^3 / 16^3 blocks of the occupancy grid (rv_probe)
-#endif
-#ifndef RV_PATCH_4X4
-#define RV_PATCH_4X4 1                 // each 16-lane column group covers a 4x4 pixel patch
-#endif
+// (software pipelining across tiles, most-expensive-first tile order and CU-local tile chunks were measured slower: profiles/HISTORY.md 1, 3.2)
 static constexpr uint32_t RV_BLOCK = RV_BLOCK_THREADS;
 static constexpr int RV_WAVES_PER_SIMD = (RV_BLOCK_THREADS / 256) * RV_BLOCKS_PER_CU;
 static constexpr int RV_WAVES = RV_BLOCK / 64;
 static constexpr uint32_t RV_LDS_W = RV_NFRAG * 1024;                  // weight fragments
 static constexpr uint32_t RV_LDS_SH = RV_WAVES * 64 * 32;              // 16 halves per lane
 static constexpr uint32_t RV_LDS_LV = 4 * 96;                          // rf_lane_levels of the 4 lane groups
-[[maybe_unused]] static constexpr uint32_t RV_LDS_CHUNK = RV_CU_CHUNKS ? 16 : 0;        // the CU's current tile chunk (one 64-bit word), k_render_frame_multi only
 
 struct rf_frame {
     const float* rays_o; const float* rays_d; uint32_t N;   // rays_o == null: the rays are those of `cam` (pixel = ray id)
@@ -156,7 +129,7 @@ struct rf_frame {
     float* image; float* depth; float* weights_sum;
     uint32_t* stats; uint32_t* queue;
 #ifdef RV_COUNTERS
-    uint32_t* hist;                                    // debug timeline (4 x 512 bins) in the tile-order area of the workspace
+    uint32_t* hist;                                    // debug timeline (4 x 512 bins) in the reserved area of the workspace
 #endif
     const uint32_t* coarse;          // [C * (H/4)^3 / 32] words, or null when H is not a power of two >= 4
     uint32_t coarse_words;           // words per cascade level
@@ -164,7 +137,6 @@ struct rf_frame {
     uint32_t skip;                   // 1: empty 4^3 / 16^3 blocks may be skipped (rv_probe); decided on the host from H, C, bound
     const uint32_t* occ_ext;         // the extent of the occupied blocks (k_build_coarse), or null: a ray marches no further than where it leaves that box
     float occ_unit, occ_top;         // world size of one unit of that lattice, and the half-width of the outermost cascade (its origin is -occ_top)
-    const uint32_t* tile_order;      // [N/64] 8x8 tiles, most expensive first (k_tile_order), or null
 };
 
 // coarse[level][m] = any fine bit set in Morton block m (64 bits = 8 bytes of the bitfield)
@@ -256,11 +228,10 @@ __device__ __forceinline__ bool rv_test(const rv_view& m, const uint32_t* __rest
 
 // Leave the empty cell tested at tc (state `st`): a verified block skip when the block is empty (ngp_march.h), else the
 // reference's step.
-template <bool SKIP>
 __device__ __forceinline__ float rv_leave(const rv_view& m, const uint32_t* __restrict__ lds_coarse, float M, const rv_tested& st, float tc) {
     const rv_point& r = st.r;
     const float tt = r.cell_exit(m, tc);
-    if (SKIP && lds_coarse && !st.maybe) {
+    if (lds_coarse && !st.maybe) {
         const int sh = ((lds_coarse[st.sw] | lds_coarse[st.sw + 1]) == 0u) ? 4 : 2;
         const float ta = ngp_try_skip(m, r, tc, tt, sh, M);
         if (ta >= 0.0f) return ta;
@@ -269,7 +240,6 @@ __device__ __forceinline__ float rv_leave(const rv_view& m, const uint32_t* __re
     return ngp_advance(m, tc, tt, tp);
 }
 
-template <bool SKIP>
 __device__ __forceinline__ bool rv_probe(const rv_ray& ray, const rv_consts& k, const uint32_t* __restrict__ lds_coarse, uint32_t coarse_words,
                                          float M, rv_block_cache& bc, float& t, float& x, float& y, float& z, float& dt
 #ifdef RV_COUNTERS
@@ -285,7 +255,7 @@ __device__ __forceinline__ bool rv_probe(const rv_ray& ray, const rv_consts& k, 
 #endif
     x = st.r.x; y = st.r.y; z = st.r.z; dt = st.r.dt;
     if (occ) return true;
-    t = rv_leave<SKIP>(m, lds_coarse, M, st, t);
+    t = rv_leave(m, lds_coarse, M, st, t);
     return false;
 }
 
@@ -358,187 +328,18 @@ __global__ __launch_bounds__(RF_BLOCK, RF_FIELD_WG_PER_CU) void k_field_forward_
 // queue index -> ray id.  With tile_w set (rays are a row-major image whose width and height are multiples of 8)
 // consecutive queue indices walk 8x8 pixel tiles, so the 64 lanes of a wave start on a compact patch of the image
 // and their gathers share cache lines; otherwise the identity.
-__device__ __forceinline__ uint32_t rv_ray_of(uint32_t idx, uint32_t tile_w, const uint32_t* __restrict__ tile_order, uint32_t n_rays = 0) {
+__device__ __forceinline__ uint32_t rv_ray_of(uint32_t idx, uint32_t tile_w) {
     if (tile_w == 0) return idx;
-    uint32_t tile = idx >> 6;
-    const uint32_t in = idx & 63u, tiles_x = tile_w >> 3;
-    if (tile_order) tile = tile_order[tile];
-#if RV_CU_CHUNKS
-    // eight consecutive tiles form a block of 4 x 2 tiles (the chunk a CU draws at once) when the image divides into such blocks (else row-major as before)
-    uint32_t ty, tx;
-    if ((tiles_x & 3u) == 0 && ((n_rays / tile_w) & 15u) == 0) {      // whole 4 x 2 blocks only: the image is a multiple of 32 x 16 pixels
-        const uint32_t c = tile >> 3, i = tile & 7u, bpr = tiles_x >> 2;
-        const uint32_t by = c / bpr, bx = c - by * bpr;
-        ty = by * 2 + (i >> 2); tx = bx * 4 + (i & 3u);
-    } else { ty = tile / tiles_x; tx = tile - ty * tiles_x; }
-#else
+    const uint32_t tile = idx >> 6, in = idx & 63u, tiles_x = tile_w >> 3;
     const uint32_t ty = tile / tiles_x, tx = tile - ty * tiles_x;
-#endif
-#if RV_PATCH_4X4
     // lanes 16p..16p+15 (one MFMA column tile, one gather instruction group) cover a compact 4x4 pixel patch
     const uint32_t p = in >> 4, s = in & 15u;
     const uint32_t px = (p & 1u) * 4 + (s & 3u), py = (p >> 1) * 4 + (s >> 2);
     return (ty * 8 + py) * tile_w + tx * 8 + px;
-#else
-    return (ty * 8 + (in >> 3)) * tile_w + tx * 8 + (in & 7u);
-#endif
 }
-
-#if RV_S == 1
-__global__ __launch_bounds__(RV_BLOCK, RV_WAVES_PER_SIMD) void k_render_frame(rf_params P, rf_frame F) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char rv_smem[];
-    ngp_h8* lds_w = reinterpret_cast<ngp_h8*>(rv_smem);
-    _Float16* lds_sh = reinterpret_cast<_Float16*>(rv_smem + RV_LDS_W);
-    uint32_t* lds_coarse = F.coarse ? reinterpret_cast<uint32_t*>(rv_smem + RV_LDS_W + RV_LDS_SH + RV_LDS_LV) : nullptr;
-
-    const int lane = threadIdx.x & 63, g = lane >> 4, s = lane & 15, wave = threadIdx.x >> 6;
-
-    // ---- stage the weight fragments (each in the k order its consumer expects) and the coarse map ----
-    rv_stage_weights(P, lds_w, wave, RV_WAVES, lane);
-    if (lds_coarse) {
-        const uint32_t nw = F.coarse_words * F.C;
-        for (uint32_t i = threadIdx.x; i < nw; i += RV_BLOCK) lds_coarse[i] = F.coarse[i];
-    }
-    // per-lane-group level constants live in LDS (re-read in each pass) instead of 24 VGPRs across the march loop
-    rf_lane_levels* lds_lv = reinterpret_cast<rf_lane_levels*>(rv_smem + RV_LDS_W + RV_LDS_SH);
-    if (wave == 0 && s == 0) {
-        rf_lane_levels tmp;
-        rf_setup_levels(P, g, tmp);
-        lds_lv[g] = tmp;
-    }
-    __syncthreads();
-    const rf_iter_class cls = rf_classify(lds_lv[g]);
-
-    _Float16* my_sh = lds_sh + (wave * 64 + lane) * 16;                // this lane's ray
-    const _Float16* wave_sh = lds_sh + wave * 64 * 16;
-
-    // wave-uniform march constants (ngp_march_t::setup's formulas), kept out of the per-ray state
-    // float conversions and divisions run on the vector ALU even for uniform inputs; rv_uniform moves the results to SGPRs
-    rv_consts K;
-    K.bound = P.bound; K.rbound = rv_uniform(1.0f / P.bound); K.dt_gamma = F.dt_gamma;
-    K.Hf = rv_uniform((float)F.H); K.Cf = rv_uniform((float)F.C); K.Hm1 = rv_uniform((float)(F.H - 1));
-    K.rH = rv_uniform(1.0f / K.Hf);
-    K.H3 = rv_uniform((float)(F.H * F.H * F.H));
-    K.dt_min = rv_uniform((2.0f * 1.7320508075688772f) / (float)F.max_steps);
-    K.dt_max = rv_uniform(((2.0f * 1.7320508075688772f) * (float)(1 << (F.C - 1))) / K.Hf);
-    K.grid = F.bitfield;
-
-    bool active = false;
-    uint32_t ray = 0, nsamp = 0;
-    rv_ray m;
-    float t = 0, last_t = 0, near = 0, far = 0;
-    float ws = 0, dacc = 0, cr = 0, cg = 0, cb = 0, tcomp = 0;
-    bool exhausted = false;
-    rv_block_cache bc;
-    uint32_t n_samples_local = 0;
-
-    for (;;) {
-        // ---- refill finished lanes from the queue (one atomic per wave) ----
-        if (!exhausted) {
-            const unsigned long long need = __ballot(!active);
-            if (need) {
-                const uint32_t cnt = (uint32_t)__popcll(need);
-                uint32_t base = 0;
-                if (lane == 0) base = atomicAdd(F.queue, cnt);
-                base = __shfl(base, 0, 64);
-                if (!active) {
-                    const uint32_t idx = base + (uint32_t)__popcll(need & ((1ull << lane) - 1ull));
-                    if (idx < F.N) {
-                        ray = rv_ray_of(idx, F.tile_w, F.tile_order);
-                        const float* o = F.rays_o + 3ull * ray;
-                        const float* d = F.rays_d + 3ull * ray;
-                        ngp_near_far_inline(o, d, F.aabb, F.min_near, near, far);
-                        m.ox = o[0]; m.oy = o[1]; m.oz = o[2];
-                        m.dx = d[0]; m.dy = d[1]; m.dz = d[2];
-                        m.rdx = 1.0f / m.dx; m.rdy = 1.0f / m.dy; m.rdz = 1.0f / m.dz;
-                        t = near; last_t = near; tcomp = near;
-                        ws = 0; dacc = 0; cr = 0; cg = 0; cb = 0; nsamp = 0;
-                        float sh[16];
-                        sh_eval<4>(m.dx, m.dy, m.dz, P.shn, sh);      // the ray's direction encoding, once per ray
-                        #pragma unroll
-                        for (int j = 0; j < 16; j++) my_sh[j] = ngp_f2h(sh[j]);
-                        active = true;
-                    }
-                }
-                if (base + cnt >= F.N) exhausted = true;
-            }
-        }
-        if (__ballot(active) == 0ull) break;            // queue drained and every ray of this wave is finished
-
-        // ---- march each active lane towards its next occupied sample (bounded probes per round) ----
-        bool has = false, ended = false;
-        float x = 0, y = 0, z = 0, dt = 0, d1 = 0;
-        if (active) {
-            int probes = 0;
-            for (;;) {
-                if (!(t < far && nsamp < F.max_steps)) { ended = true; break; }
-                if (rv_probe<false>(m, K, lds_coarse, F.coarse_words, 0.0f, bc, t, x, y, z, dt)) { has = true; break; }
-                if (++probes >= RF_PROBES_PER_ROUND) break;
-            }
-            if (has) {
-                t += dt;
-                d1 = t - last_t;
-                last_t = t;
-                nsamp++;
-            }
-        }
-
-        // ---- field evaluation: 4 passes of 16 columns ----
-        float sig = 0, sr = 0, sg = 0, sb = 0;
-        #pragma unroll 1
-        for (int p = 0; p < 4; p++) {
-            const int src = 16 * p + s;
-            const bool v = __shfl((int)has, src, 64) != 0;
-            if (__ballot(v) == 0ull) continue;           // wave-uniform: nothing to evaluate in this pass
-#ifdef RV_EXPERIMENT_SAMEPOS       // timing-only build: columns share positions in groups of RV_EXPERIMENT_SAMEPOS
-            const int psrc = 16 * p + (s & ~(RV_EXPERIMENT_SAMEPOS - 1));
-            const float qx = __shfl(x, psrc, 64), qy = __shfl(y, psrc, 64), qz = __shfl(z, psrc, 64);
-#else
-            const float qx = __shfl(x, src, 64), qy = __shfl(y, src, 64), qz = __shfl(z, src, 64);
-#endif
-            const ngp_h4 shq = *reinterpret_cast<const ngp_h4*>(wave_sh + src * 16 + 4 * g);
-            float a, b, c, d;
-            const rf_lane_levels lv = lds_lv[g];
-            rv_field_tile(P, lv, cls, lds_w, lane, qx, qy, qz, shq, a, b, c, d);
-            const float ra = __shfl(a, s, 64), rb = __shfl(b, s, 64), rc = __shfl(c, s, 64), rd = __shfl(d, s, 64);
-            if (g == p) { sig = ra; sr = rb; sg = rc; sb = rd; }
-        }
-
-        // ---- composite (kernel_composite_rays arithmetic, raymarching.cu:865-896) ----
-        bool done = ended;
-        if (has) {
-            rv_activate(P, sig, sr, sg, sb);
-            n_samples_local++;
-            const float alpha = 1.0f - ngp_expf(-sig * dt);
-            const float T = 1 - ws;
-            const float w = alpha * T;
-            ws += w;
-            tcomp += d1;
-            dacc += w * tcomp;
-            cr += w * sr; cg += w * sg; cb += w * sb;
-            if ((double)T < 1e-4) done = true;
-        }
-        if (done) {
-            F.image[3ull * ray] = cr + (1 - ws) * F.bg[0];           // nerf/renderer.py:371-372
-            F.image[3ull * ray + 1] = cg + (1 - ws) * F.bg[1];
-            F.image[3ull * ray + 2] = cb + (1 - ws) * F.bg[2];
-            F.depth[ray] = fmaxf(dacc - near, 0.0f) / (far - near);
-            F.weights_sum[ray] = ws;
-            if (nsamp >= F.max_steps && t < far) atomicAdd(F.stats + 1, 1u);
-            if (nsamp > 0) atomicAdd(F.stats + 2, 1u);
-            active = false;
-        }
-    }
-    uint32_t tot = n_samples_local;
-    #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) tot += __shfl_down(tot, off, 64);
-    if (lane == 0 && tot) atomicAdd(F.stats, tot);
-}
-
-#endif  // RV_S == 1
 
 // ---------------------------------------------------------------------------
-// k_render_frame_multi: the same frame kernel with RV_S samples per ray per round.
+// k_render_frame_multi: the frame kernel, with up to RV_S samples per ray per round.
 //
 // The march is a lock-step loop: as long as one lane of the wave is still crossing empty space the other 63 wait, and in
 // steady state some lane always is.  Here a round's march loop lets every lane collect up to RV_S samples (lanes in
@@ -547,83 +348,9 @@ __global__ __launch_bounds__(RV_BLOCK, RV_WAVES_PER_SIMD) void k_render_frame(rf
 // is evaluated tile by tile, a tile being sample k of the 16 rays of one column group; the half-precision network outputs
 // overwrite the first 8 bytes of the slot; each lane then composites its samples in order.  A ray that saturates at
 // sample j < count has marched count-1-j samples too many: they are discarded (they were never composited, so images,
-// counts and statistics are identical to the one-sample kernel); the price is their field evaluation.
+// counts and statistics are those of a one-sample-per-round march); the price is their field evaluation.
 // ---------------------------------------------------------------------------
-#if RV_S > 1
 static constexpr uint32_t RV_LDS_SMP = RV_WAVES * 64 * RV_S * 16;      // per sample: float4 (x, y, z, t before the step)
-
-// ---------------------------------------------------------------------------
-// Tile order.  A frame's rays differ a lot in cost (0 to a few hundred samples) and a lane only ever sees two or three
-// of them, so the order in which the queue hands them out decides how long the last waves run alone.  Longest first:
-// k_tile_estimate marches the centre ray of every 8x8 pixel tile through the occupancy grid and counts its samples (no
-// field evaluation); k_tile_order sorts the tiles by that count, descending (counting sort, one workgroup).  The frame
-// kernel maps queue position -> tile through the table.  Results do not depend on the order (tests: order invariance).
-// ---------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_tile_estimate(rf_frame F, float bound, uint32_t n_tiles, uint32_t* __restrict__ est) {
-    const uint32_t tile = blockIdx.x * 256 + threadIdx.x;
-    if (tile >= n_tiles) return;
-    const uint32_t tiles_x = F.tile_w >> 3;
-    const uint32_t ty = tile / tiles_x, tx = tile - ty * tiles_x;
-    const uint32_t ray = (ty * 8 + 4) * F.tile_w + tx * 8 + 4;
-    const float* o = F.rays_o + 3ull * ray;
-    const float* d = F.rays_d + 3ull * ray;
-    float near, far;
-    ngp_near_far_inline(o, d, F.aabb, F.min_near, near, far);
-    rv_ray m;
-    m.ox = o[0]; m.oy = o[1]; m.oz = o[2];
-    m.dx = d[0]; m.dy = d[1]; m.dz = d[2];
-    m.rdx = 1.0f / m.dx; m.rdy = 1.0f / m.dy; m.rdz = 1.0f / m.dz;
-    rv_consts K;
-    K.bound = bound; K.rbound = 1.0f / bound; K.dt_gamma = F.dt_gamma;
-    K.Hf = (float)F.H; K.Cf = (float)F.C; K.Hm1 = (float)(F.H - 1);
-    K.rH = 1.0f / K.Hf;
-    K.H3 = (float)(F.H * F.H * F.H);
-    K.dt_min = (2.0f * 1.7320508075688772f) / (float)F.max_steps;
-    K.dt_max = ((2.0f * 1.7320508075688772f) * (float)(1 << (F.C - 1))) / K.Hf;
-    K.grid = F.bitfield;
-    const float M = F.skip ? ngp_skip_margin(m, bound, far) : __builtin_inff();
-    float t = near;
-    uint32_t n = 0;
-    int probes = 0;
-    rv_block_cache bc;
-    while (t < far && n < 1023u && probes < 4096) {
-        float x, y, z, dt;
-#ifdef RV_COUNTERS
-        int pc;
-        if (rv_probe<true>(m, K, F.coarse, F.coarse_words, M, bc, t, x, y, z, dt, &pc)) { t += dt; n++; }
-#else
-        if (rv_probe<true>(m, K, F.coarse, F.coarse_words, M, bc, t, x, y, z, dt)) { t += dt; n++; }
-#endif
-        probes++;
-    }
-    est[tile] = n;
-}
-
-__global__ __launch_bounds__(1024) void k_tile_order(const uint32_t* __restrict__ est, uint32_t n_tiles, uint32_t* __restrict__ order) {
-    __shared__ uint32_t hist[1024];
-    __shared__ uint32_t wsum[16];
-    const uint32_t tid = threadIdx.x;
-    hist[tid] = 0;
-    __syncthreads();
-    for (uint32_t i = tid; i < n_tiles; i += 1024) atomicAdd(&hist[1023u - est[i]], 1u);      // bin 0 = most samples
-    __syncthreads();
-    // exclusive prefix sum over the 1024 bins: wave scan, then the 16 wave totals
-    const uint32_t v = hist[tid];
-    uint32_t inc = v;
-    #pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t up = __shfl_up(inc, off, 64);
-        if ((int)(tid & 63u) >= off) inc += up;
-    }
-    if ((tid & 63u) == 63u) wsum[tid >> 6] = inc;
-    __syncthreads();
-    uint32_t base = 0;
-    for (uint32_t w = 0; w < (tid >> 6); w++) base += wsum[w];
-    __syncthreads();
-    hist[tid] = base + inc - v;
-    __syncthreads();
-    for (uint32_t i = tid; i < n_tiles; i += 1024) order[atomicAdd(&hist[1023u - est[i]], 1u)] = i;
-}
 
 // The persistent loop of k_render_frame_multi.  FIXED selects compile-time iteration classes for the reference's grid
 // (iteration 0 dense, 1 mixed, 2 and 3 hashed: 16 levels from 16^3 at 2^19 rows per level): with the classes constant the
@@ -632,7 +359,7 @@ __global__ __launch_bounds__(1024) void k_tile_order(const uint32_t* __restrict_
 template <bool FIXED>
 __device__ __forceinline__ void rv_frame_loop(const rf_params& P, const rf_frame& F, const rf_iter_class cls_rt,
                                               const ngp_h8* __restrict__ lds_w, _Float16* lds_sh, const rf_lane_levels* lds_lv,
-                                              float4* lds_smp, const uint32_t* lds_coarse, unsigned long long* lds_chunk, const float* lds_occ) {
+                                              float4* lds_smp, const uint32_t* lds_coarse, const float* lds_occ) {
     const rf_iter_class cls = FIXED ? rf_iter_class{1u, 12u, 2u} : cls_rt;
     const int lane = threadIdx.x & 63, g = lane >> 4, s = lane & 15, wave = threadIdx.x >> 6;
     const int wave_s = __builtin_amdgcn_readfirstlane(wave);          // the same, known to be uniform
@@ -658,10 +385,7 @@ __device__ __forceinline__ void rv_frame_loop(const rf_params& P, const rf_frame
     float t = 0, last_t = 0, near = 0, far = 0;
     float ws = 0, dacc = 0, cr = 0, cg = 0, cb = 0, tcomp = 0;
     bool exhausted = false;
-#if RV_XCD_QUEUES
     uint32_t rv_q = blockIdx.x & 7u, rv_q_seen = 0;        // blockIdx % 8 labels the workgroups that share an XCD
-#endif
-    (void)lds_chunk;
     rv_block_cache bc;                                 // bitfield word of the block the ray last tested (block ids are global: stays valid across rays)
     uint32_t n_samples_local = 0, n_tiles = 0, n_capped_local = 0, n_hit_local = 0;
 #ifdef RV_COUNTERS
@@ -688,53 +412,6 @@ __device__ __forceinline__ void rv_frame_loop(const rf_params& P, const rf_frame
             if (need && (uint32_t)__popcll(need) >= RV_REFILL_MIN) {
                 const uint32_t cnt = (uint32_t)__popcll(need);
                 uint32_t base = 0;
-#if RV_XCD_QUEUES && RV_CU_CHUNKS && RV_REFILL_MIN == 64
-                // One 8x8 tile for this wave, out of the CU's current chunk of 8 adjacent tiles (LDS word, compare-and-swap); the wave that finds the chunk
-                // used up fetches the next one from ITS band's queue with one atomic and publishes it while the others wait.  Bands start at multiples of 8 tiles.
-                const uint32_t n_tiles64 = (F.N + 63u) >> 6;
-                uint32_t q_hi = 0;
-                {
-                    uint32_t tile = 0xFFFFFFFFu, band = rv_q;
-                    if (lane == 0) {
-                        for (;;) {
-                            const unsigned long long d = __hip_atomic_load(lds_chunk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                            const uint32_t taken = (uint32_t)(d >> 32) & 0xFFu;
-                            unsigned long long want = d;
-                            if (taken < 8u) {                  // a tile is left: take it
-                                if (__hip_atomic_compare_exchange_strong(lds_chunk, &want, d + (1ull << 32), __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) {
-                                    tile = (uint32_t)d + taken; band = (uint32_t)(d >> 40); break;
-                                }
-                            } else if (taken == 8u) {          // used up: ONE wave fetches the next chunk (state 0xFF while it does), the others wait for it
-                                if (__hip_atomic_compare_exchange_strong(lds_chunk, &want, d | (0xFFull << 32), __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) {
-                                    const uint32_t b_lo = (uint32_t)(((unsigned long long)n_tiles64 * rv_q) / RV_BANDS) & ~7u;
-                                    const uint32_t b_hi = rv_q + 1u == RV_BANDS ? n_tiles64 : ((uint32_t)(((unsigned long long)n_tiles64 * (rv_q + 1u)) / RV_BANDS) & ~7u);
-                                    const uint32_t got = atomicAdd(F.queue + 32 + rv_q, 8u) + b_lo;
-                                    if (got >= b_hi) {         // this wave's band is dry: hand the slot back, move on to the next band
-                                        __hip_atomic_store(lds_chunk, 8ull << 32, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                                        tile = 0xFFFFFFFEu; break;
-                                    }
-                                    __hip_atomic_store(lds_chunk, (unsigned long long)got | ((unsigned long long)rv_q << 40) | (1ull << 32), __ATOMIC_RELAXED,
-                                                       __HIP_MEMORY_SCOPE_WORKGROUP);
-                                    tile = got; break;
-                                }
-                            } else {
-                                __builtin_amdgcn_s_sleep(4);   // a fetch is in flight (one global atomic: ~2 us)
-                            }
-                        }
-                    }
-                    tile = __shfl(tile, 0, 64); band = __shfl(band, 0, 64);
-                    if (tile == 0xFFFFFFFEu) {             // band dry: move on (same walk as the plain queues), try again next round
-                        rv_q += 8u;
-                        if (rv_q >= RV_BANDS) rv_q = (rv_q + 1u) & 7u;
-                        if (++rv_q_seen == RV_BANDS) exhausted = true;
-                        continue;
-                    }
-                    const uint32_t t_hi = band + 1u == RV_BANDS ? n_tiles64 : ((uint32_t)(((unsigned long long)n_tiles64 * (band + 1u)) / RV_BANDS) & ~7u);
-                    base = tile << 6;
-                    q_hi = tile < t_hi ? ((tile + 1u) << 6) : 0u;                                // a chunk may reach past its band's end: those tiles are nobody's
-                    q_hi = q_hi < F.N ? q_hi : F.N;
-                }
-#elif RV_XCD_QUEUES
                 // Queue q holds the rays of image band q (tiles [T q / RV_BANDS, T (q + 1) / RV_BANDS) of 64 rays): the workgroups of one XCD
                 // work on the same band, so that the table lines neighbouring rays share are fetched into ONE L2 and
                 // not into eight.  A wave that finds its queue empty moves on to its XCD's next band, then to the other XCDs'.
@@ -744,18 +421,10 @@ __device__ __forceinline__ void rv_frame_loop(const rf_params& P, const rf_frame
                 q_hi = q_hi < F.N ? q_hi : F.N;
                 if (lane == 0) base = atomicAdd(F.queue + 32 + rv_q, cnt);
                 base = __shfl(base, 0, 64) + q_lo;
-#else
-                if (lane == 0) base = atomicAdd(F.queue, cnt);
-                base = __shfl(base, 0, 64);
-#endif
                 if (!active) {
                     const uint32_t idx = base + (uint32_t)__popcll(need & ((1ull << lane) - 1ull));
-#if RV_XCD_QUEUES
                     if (idx < q_hi) {
-#else
-                    if (idx < F.N) {
-#endif
-                        ray = rv_ray_of(idx, F.tile_w, F.tile_order, F.N);
+                        ray = rv_ray_of(idx, F.tile_w);
                         float o[3], d[3];
                         if (F.rays_o) {
                             #pragma unroll
@@ -789,9 +458,6 @@ __device__ __forceinline__ void rv_frame_loop(const rf_params& P, const rf_frame
                         active = true;
                     }
                 }
-#if RV_XCD_QUEUES && RV_CU_CHUNKS && RV_REFILL_MIN == 64
-                (void)cnt;
-#elif RV_XCD_QUEUES
                 if (base + cnt >= q_hi) {                  // this queue has run dry: move on, until all eight have been seen
                     // XCD x owns bands x, x + 8, x + 16, ...: thin bands spread over the whole image, so that every XCD gets a fair sample of cheap and
                     // expensive rows; when its own are done it goes on with the next XCD's
@@ -799,9 +465,6 @@ __device__ __forceinline__ void rv_frame_loop(const rf_params& P, const rf_frame
                     if (rv_q >= RV_BANDS) rv_q = (rv_q + 1u) & 7u;
                     if (++rv_q_seen == RV_BANDS) exhausted = true;
                 }
-#else
-                if (base + cnt >= F.N) exhausted = true;
-#endif
             }
         }
         if (__ballot(active) == 0ull) {
@@ -848,11 +511,11 @@ __device__ __forceinline__ void rv_frame_loop(const rf_params& P, const rf_frame
                     float x, y, z, dt;
 #ifdef RV_COUNTERS
                     int pc = 0;
-                    const bool hit = rv_probe<RV_BLOCK_SKIP != 0>(mr, Kr, lds_coarse, F.coarse_words, M, bc, t, x, y, z, dt, &pc);
+                    const bool hit = rv_probe(mr, Kr, lds_coarse, F.coarse_words, M, bc, t, x, y, z, dt, &pc);
                     n_probe[pc]++;
                     if (hit) {
 #else
-                    if (rv_probe<RV_BLOCK_SKIP != 0>(mr, Kr, lds_coarse, F.coarse_words, M, bc, t, x, y, z, dt)) {
+                    if (rv_probe(mr, Kr, lds_coarse, F.coarse_words, M, bc, t, x, y, z, dt)) {
 #endif
                         smp_w[cnt] = make_float4(x, y, z, t);     // the compositor re-derives dt and t - last_t from t (same operations)
                         t += dt;
@@ -887,60 +550,6 @@ __device__ __forceinline__ void rv_frame_loop(const rf_params& P, const rf_frame
 
         RV_TICK(c_march)
         // ---- field evaluation: for each group of 16 rays, tile k = their k-th samples ----
-#if RV_PIPELINE
-        {
-            // Software pipeline across tiles: ALL gathers of the next tile are issued before the MLP of the current one, so a
-            // wave keeps the texture path busy while it sits in its 36-MFMA chain (two waves per SIMD do not overlap the
-            // phases by themselves).  Costs 47 registers across the MLP (32 rows, 12 fractions, the position).
-            // kmax[p] = most samples any ray of lane group p holds: tile (p, k) exists for k < kmax[p]
-            int km = cnt;
-            #pragma unroll
-            for (int off = 1; off < 16; off <<= 1) {
-                const int o = __shfl_xor(km, off, 64);
-                km = o > km ? o : km;
-            }
-            int kmax[4];
-            #pragma unroll
-            for (int p = 0; p < 4; p++) kmax[p] = __builtin_amdgcn_readlane(km, 16 * p);
-            auto first_group = [&](int p) { while (p < 4 && kmax[p < 4 ? p : 3] == 0) p++; return p; };
-            const rf_lane_levels lv = lds_lv[g];
-            rf_pair na, nb;                            // rows of the tile in flight
-            int p = first_group(0), k = 0;
-            auto issue = [&](int pp, int kk) {
-                const int src = 16 * pp + s;
-                float4 q = wave_smp[src * RV_S + kk];
-                if (!(__shfl(cnt, src, 64) > kk)) q = make_float4(0.f, 0.f, 0.f, 0.f);
-                float x0, x1, x2;
-                rf_normalise(P, q.x, q.y, q.z, x0, x1, x2);
-                rf_gather_pair<0>(P, lv, cls, x0, x1, x2, na);
-                rf_gather_pair<1>(P, lv, cls, x0, x1, x2, nb);
-            };
-            if (p < 4) issue(p, 0);
-            #pragma unroll 1
-            while (p < 4) {
-                const int src = 16 * p + s;
-                const bool valid = __shfl(cnt, src, 64) > k;
-                const ngp_h4 shq = *reinterpret_cast<const ngp_h4*>(wave_sh + src * 16 + 4 * g);
-                n_tiles++;
-                ngp_h8 x;
-                rf_blend_pair(na, 0, x);
-                rf_blend_pair(nb, 1, x);
-                int p1 = p, k1 = k + 1;                // the next tile
-                if (k1 >= kmax[p]) { p1 = first_group(p + 1); k1 = 0; }
-                if (p1 < 4) issue(p1, k1);
-                __builtin_amdgcn_sched_barrier(0);       // the prefetch stays above the MLP
-                float a, b, c, d;
-                rv_mlp_tile(lds_w, lane, x, shq, a, b, c, d);
-                if (g == 0 && valid) {                   // the half-precision network outputs replace (x, y) of the slot
-                    ngp_h4 r;
-                    r[0] = (_Float16)a; r[1] = (_Float16)b; r[2] = (_Float16)c; r[3] = (_Float16)d;
-                    *reinterpret_cast<ngp_h4*>(&wave_smp[src * RV_S + k]) = r;
-                }
-                p = p1; k = k1;
-            }
-        }
-#else
-#if RV_SORT_COLUMNS
         // Tile columns in order of decreasing sample count: lane group p evaluates the rays ranked 16p .. 16p+15, so the rays
         // of a group hold about the same number of samples and few columns of its tiles are dummies (a group runs
         // max-count tiles).  Counting sort over the 0..RV_S possible counts with ballots; `col_src` = the lane whose samples
@@ -957,19 +566,13 @@ __device__ __forceinline__ void rv_frame_loop(const rf_params& P, const rf_frame
             }
             col_src = __builtin_amdgcn_ds_permute((int)(rank << 2), (int)below_me);
         }
-#endif
         #pragma unroll 1
         for (int p = 0; p < 4; p++) {
-#if RV_SORT_COLUMNS
             const int src = __shfl(col_src, 16 * p + s, 64);
-#else
-            const int src = 16 * p + s;
-#endif
             const int ccol = __shfl(cnt, src, 64);
             if (__ballot(ccol > 0) == 0ull) continue;
             const ngp_h4 shq = *reinterpret_cast<const ngp_h4*>(wave_sh + src * 16 + 4 * g);
             const rf_lane_levels lv = lds_lv[g];
-#if RV_TILE_PAIRS
             // tiles k and k+1 of the group together (the same 16 rays, consecutive samples): two MFMA chains per pass
             #pragma unroll 1
             for (int k = 0; k < RV_S; k += 2) {
@@ -1006,24 +609,7 @@ __device__ __forceinline__ void rv_frame_loop(const rf_params& P, const rf_frame
                     }
                 }
             }
-#else
-            #pragma unroll 1
-            for (int k = 0; k < RV_S; k++) {
-                if (__ballot(ccol > k) == 0ull) break;   // counts only shrink with k
-                float4 q = wave_smp[src * RV_S + k];
-                if (!(ccol > k)) q = make_float4(0.f, 0.f, 0.f, 0.f);   // column without a k-th sample: harmless dummy
-                n_tiles++;
-                float a, b, c, d;
-                rv_field_tile(P, lv, cls, lds_w, lane, q.x, q.y, q.z, shq, a, b, c, d);
-                if (g == 0 && ccol > k) {                // the half-precision network outputs replace (x, y) of the slot
-                    ngp_h4 r;
-                    r[0] = (_Float16)a; r[1] = (_Float16)b; r[2] = (_Float16)c; r[3] = (_Float16)d;
-                    *reinterpret_cast<ngp_h4*>(&wave_smp[src * RV_S + k]) = r;
-                }
-            }
-#endif
         }
-#endif
 
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
@@ -1127,14 +713,10 @@ __global__ __launch_bounds__(RV_BLOCK, RV_WAVES_PER_SIMD) void k_render_frame_mu
     ngp_h8* lds_w = reinterpret_cast<ngp_h8*>(rv_smem);
     _Float16* lds_sh = reinterpret_cast<_Float16*>(rv_smem + RV_LDS_W);
     rf_lane_levels* lds_lv = reinterpret_cast<rf_lane_levels*>(rv_smem + RV_LDS_W + RV_LDS_SH);
-    float4* lds_smp = reinterpret_cast<float4*>(rv_smem + RV_LDS_W + RV_LDS_SH + RV_LDS_LV + RV_LDS_CHUNK);
-    uint32_t* lds_coarse = F.coarse ? reinterpret_cast<uint32_t*>(rv_smem + RV_LDS_W + RV_LDS_SH + RV_LDS_LV + RV_LDS_CHUNK + RV_LDS_SMP) : nullptr;
-    unsigned long long* rv_chunk_p = reinterpret_cast<unsigned long long*>(rv_smem + RV_LDS_W + RV_LDS_SH + RV_LDS_LV);   // (RV_CU_CHUNKS only)
+    float4* lds_smp = reinterpret_cast<float4*>(rv_smem + RV_LDS_W + RV_LDS_SH + RV_LDS_LV);
+    uint32_t* lds_coarse = F.coarse ? reinterpret_cast<uint32_t*>(rv_smem + RV_LDS_W + RV_LDS_SH + RV_LDS_LV + RV_LDS_SMP) : nullptr;
 
     const int lane = threadIdx.x & 63, g = lane >> 4, s = lane & 15, wave = threadIdx.x >> 6;
-#if RV_CU_CHUNKS
-    if (threadIdx.x == 0) *rv_chunk_p = 8ull << 32;    // {first tile of the CU's current chunk : 32 | tiles taken : 8 | band : 24}; "all 8 taken": the first wave to ask fetches one
-#endif
 
     rv_stage_weights(P, lds_w, wave, RV_WAVES, lane);
     if (lds_coarse) {
@@ -1160,11 +742,10 @@ __global__ __launch_bounds__(RV_BLOCK, RV_WAVES_PER_SIMD) void k_render_frame_mu
     __syncthreads();
     const rf_iter_class cls = rf_classify(lds_lv[g]);
     if (cls.dense == 1u && cls.select == 2u && cls.hashed == 12u)
-        rv_frame_loop<true>(P, F, cls, lds_w, lds_sh, lds_lv, lds_smp, lds_coarse, rv_chunk_p, lds_occ);
+        rv_frame_loop<true>(P, F, cls, lds_w, lds_sh, lds_lv, lds_smp, lds_coarse, lds_occ);
     else
-        rv_frame_loop<false>(P, F, cls, lds_w, lds_sh, lds_lv, lds_smp, lds_coarse, rv_chunk_p, lds_occ);
+        rv_frame_loop<false>(P, F, cls, lds_w, lds_sh, lds_lv, lds_smp, lds_coarse, lds_occ);
 }
-#endif  // RV_S > 1
 
 static inline bool rv_pow2(uint32_t v) { return v && !(v & (v - 1)); }
 
@@ -1175,10 +756,12 @@ extern "C" int ngp_render_set_occupied_box(int enabled) { return rv_occ_box_enab
 static std::atomic<int> rv_block_skip_enabled{1};
 extern "C" int ngp_render_set_block_skip(int enabled) { return rv_block_skip_enabled.exchange(enabled ? 1 : 0, std::memory_order_relaxed); }
 
-static constexpr size_t RV_WS_COARSE = 256, RV_WS_TILES = 256 + 48 * 1024;   // header: global queue + debug words | 8 band queues
+// header: debug words (RV_COUNTERS builds) | extent of the occupied blocks (words 26..31) | band queues (words 32..63)
+static constexpr size_t RV_WS_COARSE = 256, RV_WS_AREA = 256 + 48 * 1024;
 extern "C" size_t ngp_render_frame_workspace(uint32_t N) {
-    // ray queue | coarse occupancy map (<= 48 KiB) | per-tile estimates and tile order (one u32 each per 64 rays)
-    return RV_WS_TILES + 2 * sizeof(uint32_t) * (size_t)ngp_div_up(N, 64u);
+    // header | coarse occupancy map (<= 48 KiB) | an area of two u32 per 64 rays: the RV_TIMELINE build's histogram, unused otherwise.  The size
+    // is part of the C ABI (callers allocate it; the cameras of ngp_render_frames_camera follow it), so the area stays reserved.
+    return RV_WS_AREA + 2 * sizeof(uint32_t) * (size_t)ngp_div_up(N, 64u);
 }
 
 static int rv_fill_camera(const char* who, const float* pose_host, const float* intrinsics_host, uint32_t H, uint32_t W, ngp_camera& cam) {
@@ -1216,7 +799,7 @@ static int rv_render_frame(const ngp_field_t* field_host, const float* rays_o, c
     F.cam = cam ? *cam : ngp_camera{};
     F.cams = nullptr; F.frame_rays = N;
     if (cam && n_cams > 1) {
-        // the cameras travel in the workspace, behind the coarse occupancy map and the tile area (pageable host memory: the copy is staged before the call returns)
+        // the cameras travel in the workspace, behind the coarse occupancy map and the reserved area (pageable host memory: the copy is staged before the call returns)
         const size_t at = (ngp_render_frame_workspace(N) + 255) & ~(size_t)255;
         NGP_REQUIRE(workspace_bytes >= at + n_cams * sizeof(ngp_camera), "render_frames_camera: workspace too small (ngp_render_frames_workspace)");
         ngp_camera* dst = reinterpret_cast<ngp_camera*>(reinterpret_cast<unsigned char*>(workspace) + at);
@@ -1232,8 +815,8 @@ static int rv_render_frame(const ngp_field_t* field_host, const float* rays_o, c
 #ifdef RV_COUNTERS
     F.hist = nullptr;
 #ifdef RV_TIMELINE                                      // the timeline's atomics perturb the cycle counters: a build of its own
-    if (workspace_bytes >= RV_WS_TILES + 2048 * sizeof(uint32_t)) {
-        F.hist = reinterpret_cast<uint32_t*>(reinterpret_cast<unsigned char*>(workspace) + RV_WS_TILES);
+    if (workspace_bytes >= RV_WS_AREA + 2048 * sizeof(uint32_t)) {
+        F.hist = reinterpret_cast<uint32_t*>(reinterpret_cast<unsigned char*>(workspace) + RV_WS_AREA);
         if (hipMemsetAsync(F.hist, 0, 2048 * sizeof(uint32_t), s) != hipSuccess) return ngp_fail(NGP_ELAUNCH, "render_frame: memset failed");
     }
 #endif
@@ -1245,13 +828,8 @@ static int rv_render_frame(const ngp_field_t* field_host, const float* rays_o, c
     // coarse occupancy (needs Morton blocks: H a power of two >= 4) in the workspace, then in LDS
     F.coarse = nullptr; F.coarse_words = 0; F.skip = 0; F.occ_ext = nullptr; F.occ_unit = 0.0f; F.occ_top = 0.0f;
     static_assert(sizeof(rf_lane_levels) * 4 == RV_LDS_LV, "LDS carve of the level table");
-    size_t lds = RV_LDS_W + RV_LDS_SH + RV_LDS_LV;
-#if RV_S > 1
-    lds += RV_LDS_SMP + RV_LDS_CHUNK;
+    size_t lds = RV_LDS_W + RV_LDS_SH + RV_LDS_LV + RV_LDS_SMP;
     const void* kernel = reinterpret_cast<const void*>(k_render_frame_multi);
-#else
-    const void* kernel = reinterpret_cast<const void*>(k_render_frame);
-#endif
     const uint64_t blocks_per_level = (uint64_t)Hgrid * Hgrid * Hgrid / 64;
     const uint64_t coarse_bytes = (uint64_t)C * blocks_per_level / 8;
     // (C * H^3 <= 2^24: the reference forms the cell index in binary32, raymarching.cu:783; beyond that it rounds)
@@ -1266,7 +844,6 @@ static int rv_render_frame(const ngp_field_t* field_host, const float* rays_o, c
         lds += coarse_bytes;
         // block skipping and the occupied box need the cascades nested in powers of two (see below)
         uint32_t* ext = nullptr;
-#if RV_S > 1
         int e2;
         const bool nested = Hgrid >= 64 && (C == 1 || frexpf(field_host->bound, &e2) == 0.5f);
         if (nested && rv_occ_box_enabled.load(std::memory_order_relaxed) && lds + 32 <= 160 * 1024) {
@@ -1276,7 +853,6 @@ static int rv_render_frame(const ngp_field_t* field_host, const float* rays_o, c
             F.occ_unit = 2.0f * (C == 1 ? field_host->bound : 1.0f) / (float)(Hgrid / 4);
             lds += 32;
         }
-#endif
         hipLaunchKernelGGL(k_build_coarse, dim3(ngp_div_up(n_blocks_total / 32, 256)), dim3(256), 0, s, bitfield, n_blocks_total, coarse,
                            (uint32_t)blocks_per_level, C, ext);
         // block skipping needs the 16^3 blocks aligned with the cascade boundaries (cells H/4 and 3H/4 of the next level) and
@@ -1285,17 +861,6 @@ static int rv_render_frame(const ngp_field_t* field_host, const float* rays_o, c
         F.skip = (rv_block_skip_enabled.load(std::memory_order_relaxed) && Hgrid >= 64 && (C == 1 || frexpf(field_host->bound, &e) == 0.5f)) ? 1u : 0u;
     }
     NGP_REQUIRE(lds <= 160 * 1024, "render_frame: LDS carve exceeds 160 KiB");
-    F.tile_order = nullptr;
-#if RV_TILE_ORDER
-    if (F.tile_w && F.coarse && workspace_bytes >= ngp_render_frame_workspace(N)) {
-        const uint32_t n_tiles = N / 64;
-        uint32_t* est = reinterpret_cast<uint32_t*>(reinterpret_cast<unsigned char*>(workspace) + RV_WS_TILES);
-        uint32_t* order = est + n_tiles;
-        hipLaunchKernelGGL(k_tile_estimate, dim3(ngp_div_up(n_tiles, 256u)), dim3(256), 0, s, F, P.bound, n_tiles, est);
-        hipLaunchKernelGGL(k_tile_order, dim3(1), dim3(1024), 0, s, est, n_tiles, order);
-        F.tile_order = order;
-    }
-#endif
     // the raised dynamic-LDS limit is a per-device function attribute: set it once on every device this process renders on
     static std::atomic<unsigned long long> attr_devices{0};
     int device = 0;
@@ -1310,11 +875,7 @@ static int rv_render_frame(const ngp_field_t* field_host, const float* rays_o, c
     uint32_t blocks = 256 * RV_BLOCKS_PER_CU;
     const uint32_t need = ngp_div_up(N, RV_BLOCK);
     if (blocks > need) blocks = need;
-#if RV_S > 1
     hipLaunchKernelGGL(k_render_frame_multi, dim3(blocks), dim3(RV_BLOCK), lds, s, P, F);
-#else
-    hipLaunchKernelGGL(k_render_frame, dim3(blocks), dim3(RV_BLOCK), lds, s, P, F);
-#endif
     NGP_CHECK_LAUNCH("render_frame");
     return NGP_OK;
 }

@@ -76,7 +76,8 @@ def _grad_worker(rank, world, port, out):
         w2.grad = None                                               # a parameter that got no gradient on this rank
         ex = GradExchange([table, w1, w2, frozen], big_numel=4096)
         ex()
-        out.put((rank, float(table.grad.mean()), w1.grad.clone(), w2.grad.clone(), len(ex.big), len(ex.small)))
+        # arrays by value: tensors would travel as shared-memory handles that die with this process (the parent may unpickle after it exits)
+        out.put((rank, float(table.grad.mean()), w1.grad.numpy().copy(), w2.grad.numpy().copy(), len(ex.big), len(ex.small)))
     finally:
         dist.destroy_process_group()
 
@@ -97,7 +98,7 @@ def test_two_rank_gradient_exchange():
     base = torch.arange(64 * 32, dtype=torch.float32).view(64, 32)
     for rank, tmean, w1g, w2g, nbig, nsmall in res:
         assert tmean == 1.5 and nbig == 1 and nsmall == 2            # (1 + 2) / 2
-        assert torch.equal(w1g, base * 1.5) and torch.equal(w2g, torch.zeros(16))
+        assert torch.equal(torch.from_numpy(w1g), base * 1.5) and torch.equal(torch.from_numpy(w2g), torch.zeros(16))
 
 
 class _MockField(torch.nn.Module):
