@@ -447,6 +447,10 @@ int ngp_render_set_block_skip(int enabled);
 /* Validation switch, process-wide, default 1: a ray of ngp_render_frame marches no further than where it leaves the box of everything occupied in the
  * grid (beyond it every cell is empty: the reference tests those cells and finds nothing).  0 = to its own far.  Results are identical; returns the previous setting. */
 int ngp_render_set_occupied_box(int enabled);
+/* Validation switch, process-wide, default 1: when the rays are an image (image_width set) ngp_render_frame estimates every 8x8 tile's cost from the
+ * coarse occupancy map and hands out each image band's tiles by decreasing cost, so that the frame ends on cheap tiles.  0 = row-major tiles.
+ * Validation and A/B only: results are identical either way; returns the previous setting. */
+int ngp_render_set_tile_order(int enabled);
 int ngp_render_frame(const ngp_field_t* field_host, const float* rays_o, const float* rays_d, uint32_t N,
                      uint32_t image_width, const float* aabb, float min_near, const uint8_t* bitfield, uint32_t C, uint32_t Hgrid,
                      float dt_gamma, uint32_t max_steps, const float* bg_color3_host,

@@ -109,7 +109,8 @@ static_assert(RV_S >= 2, "RV_S must be at least 2: the one-sample-per-round fram
 #ifndef RV_BLOCKS_PER_CU
 #define RV_BLOCKS_PER_CU 1             // the sample slots (96 KiB at 512 x 12) only fit beside ONE copy of the weights per CU
 #endif
-// (software pipelining across tiles, most-expensive-first tile order and CU-local tile chunks were measured slower: profiles/HISTORY.md 1, 3.2)
+// (software pipelining across tiles, a global most-expensive-first tile order and CU-local tile chunks were measured slower: profiles/HISTORY.md 1, 3.2;
+//  most-expensive-first WITHIN each band, from a per-frame estimate, is kept: k_tile_cost, profiles/HISTORY.md 5.1)
 static constexpr uint32_t RV_BLOCK = RV_BLOCK_THREADS;
 static constexpr int RV_WAVES_PER_SIMD = (RV_BLOCK_THREADS / 256) * RV_BLOCKS_PER_CU;
 static constexpr int RV_WAVES = RV_BLOCK / 64;
@@ -137,6 +138,7 @@ struct rf_frame {
     uint32_t skip;                   // 1: empty 4^3 / 16^3 blocks may be skipped (rv_probe); decided on the host from H, C, bound
     const uint32_t* occ_ext;         // the extent of the occupied blocks (k_build_coarse), or null: a ray marches no further than where it leaves that box
     float occ_unit, occ_top;         // world size of one unit of that lattice, and the half-width of the outermost cascade (its origin is -occ_top)
+    const uint32_t* tile_perm;       // tile_w != 0: queue position -> 8x8 tile, each band's tiles by decreasing estimated cost (k_tile_sort), or null: row-major
 };
 
 // coarse[level][m] = any fine bit set in Morton block m (64 bits = 8 bytes of the bitfield)
@@ -325,6 +327,22 @@ __global__ __launch_bounds__(RF_BLOCK, RF_FIELD_WG_PER_CU) void k_field_forward_
     else rf_points_loop<false>(P, cls, lv, lds_w, xyzs, dirs, M, sigmas, rgbs, rgb_half);
 }
 
+// ray id -> origin and direction: explicit rays, the camera of the ray's frame, or the one camera (get_rays fused, nerf/utils.py:98-108)
+__device__ __forceinline__ void rv_ray_od(const rf_frame& F, uint32_t ray, float o[3], float d[3]) {
+    if (F.rays_o) {
+        #pragma unroll
+        for (int k = 0; k < 3; k++) { o[k] = F.rays_o[3ull * ray + k]; d[k] = F.rays_d[3ull * ray + k]; }
+    } else if (F.cams) {               // camera mode, several frames per launch: the frame's camera from memory (a tile lies in one frame)
+        const uint32_t f = ray / F.frame_rays;
+        const ngp_camera c = F.cams[f];
+        o[0] = c.t[0]; o[1] = c.t[1]; o[2] = c.t[2];
+        ngp_camera_ray(c, ray - f * F.frame_rays, d);
+    } else {
+        o[0] = F.cam.t[0]; o[1] = F.cam.t[1]; o[2] = F.cam.t[2];
+        ngp_camera_ray(F.cam, ray, d);
+    }
+}
+
 // queue index -> ray id.  With tile_w set (rays are a row-major image whose width and height are multiples of 8)
 // consecutive queue indices walk 8x8 pixel tiles, so the 64 lanes of a wave start on a compact patch of the image
 // and their gathers share cache lines; otherwise the identity.
@@ -424,20 +442,10 @@ __device__ __forceinline__ void rv_frame_loop(const rf_params& P, const rf_frame
                 if (!active) {
                     const uint32_t idx = base + (uint32_t)__popcll(need & ((1ull << lane) - 1ull));
                     if (idx < q_hi) {
-                        ray = rv_ray_of(idx, F.tile_w);
+                        // the band's tiles are handed out by decreasing estimated cost (tile_perm stays within the band), so that its cheapest tiles end the frame
+                        ray = rv_ray_of(F.tile_perm ? (F.tile_perm[idx >> 6] << 6) | (idx & 63u) : idx, F.tile_w);
                         float o[3], d[3];
-                        if (F.rays_o) {
-                            #pragma unroll
-                            for (int k = 0; k < 3; k++) { o[k] = F.rays_o[3ull * ray + k]; d[k] = F.rays_d[3ull * ray + k]; }
-                        } else if (F.cams) {               // camera mode, several frames per launch: the frame's camera from memory (a tile lies in one frame)
-                            const uint32_t f = ray / F.frame_rays;
-                            const ngp_camera c = F.cams[f];
-                            o[0] = c.t[0]; o[1] = c.t[1]; o[2] = c.t[2];
-                            ngp_camera_ray(c, ray - f * F.frame_rays, d);
-                        } else {                           // camera mode: get_rays fused into the refill (nerf/utils.py:98-108)
-                            o[0] = F.cam.t[0]; o[1] = F.cam.t[1]; o[2] = F.cam.t[2];
-                            ngp_camera_ray(F.cam, ray, d);
-                        }
+                        rv_ray_od(F, ray, o, d);
                         ngp_near_far_inline(o, d, F.aabb, F.min_near, near, far);
                         if (lds_occ) {
                             // `far` is from here on where the MARCH stops: no later than a little behind the box of everything occupied (beyond it every
@@ -460,7 +468,8 @@ __device__ __forceinline__ void rv_frame_loop(const rf_params& P, const rf_frame
                 }
                 if (base + cnt >= q_hi) {                  // this queue has run dry: move on, until all eight have been seen
                     // XCD x owns bands x, x + 8, x + 16, ...: thin bands spread over the whole image, so that every XCD gets a fair sample of cheap and
-                    // expensive rows; when its own are done it goes on with the next XCD's
+                    // expensive rows; when its own are done it goes on with the next XCD's (top to bottom: ordering the bands by their estimated cost
+                    // instead was measured slower, profiles/HISTORY.md 5.1)
                     rv_q += 8u;
                     if (rv_q >= RV_BANDS) rv_q = (rv_q + 1u) & 7u;
                     if (++rv_q_seen == RV_BANDS) exhausted = true;
@@ -747,6 +756,91 @@ __global__ __launch_bounds__(RV_BLOCK, RV_WAVES_PER_SIMD) void k_render_frame_mu
         rv_frame_loop<false>(P, F, cls, lds_w, lds_sh, lds_lv, lds_smp, lds_coarse, lds_occ);
 }
 
+// ---------------------------------------------------------------------------
+// Tile order (F.tile_w != 0 and a coarse map).  A wave's unit of work is one 8x8 tile, about a fifth of its life, so the last tiles to be handed
+// out decide when the frame ends.  Each band queue therefore hands out its tiles by decreasing estimated cost: the band's cheap tiles come
+// last, whatever the view.  Results do not depend on the order (each ray's arithmetic is its own, the statistics are integer sums).
+//
+// k_tile_cost: one wave per tile.  Lane j looks at point j of 64 equally spaced points on each of 5 rays of the tile (its corners and its
+// centre), between the ray's near and where its march ends (the occupied box), and counts the steps of that 1/64 of the ray when the point's
+// 4^3 block is occupied (the coarse map of k_build_coarse, the same lattice point -> level / cell arithmetic as the march).  The estimate
+// is the tile's expected number of samples; it only has to rank tiles.
+// ---------------------------------------------------------------------------
+static constexpr uint32_t RV_ORDER_MAX = 4096;           // tiles per band that k_tile_sort ranks in LDS (16 KiB); beyond that the bands stay row-major
+
+__global__ __launch_bounds__(256) void k_tile_cost(rf_frame F, float bound, uint32_t n_tiles, uint32_t* __restrict__ cost) {
+    const uint32_t tile = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+    if (tile >= n_tiles) return;
+    rv_consts K;
+    K.bound = bound; K.rbound = 1.0f / bound; K.dt_gamma = F.dt_gamma;
+    K.Hf = (float)F.H; K.Cf = (float)F.C; K.Hm1 = (float)(F.H - 1); K.rH = 1.0f / K.Hf; K.H3 = (float)(F.H * F.H * F.H);
+    K.dt_min = (2.0f * 1.7320508075688772f) / (float)F.max_steps;
+    K.dt_max = ((2.0f * 1.7320508075688772f) * (float)(1 << (F.C - 1))) / K.Hf;
+    K.grid = F.bitfield;
+    float box[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};  // the occupied box as the frame kernel forms it (k_render_frame_multi's prologue)
+    if (F.occ_ext) {
+        const bool any = F.occ_ext[3] != 0u;
+        #pragma unroll
+        for (int k = 0; k < 3; k++) {
+            const uint32_t hi = F.occ_ext[3 + k], lo = (1u << 20) - F.occ_ext[k];
+            box[k] = any ? -F.occ_top + ((float)lo - 1.0f) * F.occ_unit : 3.0e38f;
+            box[3 + k] = any ? -F.occ_top + ((float)hi + 1.0f) * F.occ_unit : 3.1e38f;
+        }
+        box[6] = 2.0f * K.dt_max;
+    }
+    const uint32_t tiles_x = F.tile_w >> 3, ty = tile / tiles_x, tx = tile - ty * tiles_x;
+    float acc = 0.0f;
+    #pragma unroll
+    for (int r = 0; r < 5; r++) {
+        const uint32_t px = r == 4 ? 4u : (r & 1) * 7u, py = r == 4 ? 4u : (r >> 1) * 7u;
+        float o[3], d[3], near, far;
+        rv_ray_od(F, (ty * 8u + py) * F.tile_w + tx * 8u + px, o, d);
+        ngp_near_far_inline(o, d, F.aabb, F.min_near, near, far);
+        if (F.occ_ext) {
+            float n2, f2;
+            ngp_near_far_inline(o, d, box, 0.0f, n2, f2);
+            far = f2 == 3.402823466e+38f ? near : fminf(far, f2 + box[6]);
+        }
+        rv_ray m;
+        m.ox = o[0]; m.oy = o[1]; m.oz = o[2]; m.dx = d[0]; m.dy = d[1]; m.dz = d[2]; m.rdx = m.rdy = m.rdz = 0.0f;
+        const rv_view v(m, K);
+        const float seg = far > near ? (far - near) * (1.0f / 64.0f) : 0.0f;     // a ray that misses the box costs nothing
+        rv_point pt;
+        pt.at(v, (far > near ? near : 0.0f) + ((float)lane + 0.5f) * seg);
+        const uint32_t blk = ngp_morton3((uint32_t)pt.nx, (uint32_t)pt.ny, (uint32_t)pt.nz) >> 6;
+        if ((F.coarse[(uint32_t)pt.level * F.coarse_words + (blk >> 5)] >> (blk & 31u)) & 1u) acc += seg / pt.dt;
+    }
+    #pragma unroll
+    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
+    if (lane == 0) cost[tile] = (uint32_t)fminf(acc + 0.5f, 4.0e9f);
+}
+
+// k_tile_sort: one workgroup per band.  perm[the band's positions] = its tiles by decreasing cost, ties in row-major order: tile i goes to
+// position lo + #{j : c_j > c_i, or c_j == c_i and j < i} (costs in LDS, zero-padded to a multiple of 4 -- a zero after the band never ranks
+// before a tile of it -- and read 4 at a time; n^2 / 1024 comparisons per thread, the band is small).
+__global__ __launch_bounds__(1024) void k_tile_sort(const uint32_t* __restrict__ cost, uint32_t n_tiles, uint32_t* __restrict__ perm) {
+    __shared__ __attribute__((aligned(16))) uint32_t c[RV_ORDER_MAX];
+    const uint32_t b = blockIdx.x;
+    const uint32_t lo = (uint32_t)(((unsigned long long)n_tiles * b) / RV_BANDS), hi = (uint32_t)(((unsigned long long)n_tiles * (b + 1u)) / RV_BANDS);
+    const uint32_t n = hi - lo, n4 = (n + 3u) & ~3u;     // n <= RV_ORDER_MAX (host), a multiple of 4 apart
+    for (uint32_t i = threadIdx.x; i < n4; i += 1024u) c[i] = i < n ? cost[lo + i] : 0u;
+    __syncthreads();
+    const uint4* c4 = reinterpret_cast<const uint4*>(c);
+    for (uint32_t i = threadIdx.x; i < n; i += 1024u) {
+        const uint32_t ci = c[i];
+        uint32_t rank = 0;
+        #pragma unroll 4
+        for (uint32_t j = 0; j < n4; j += 4u) {
+            const uint4 q = c4[j >> 2];                  // the same 16 bytes for every lane: an LDS broadcast
+            rank += (q.x > ci || (q.x == ci && j < i)) ? 1u : 0u;
+            rank += (q.y > ci || (q.y == ci && j + 1u < i)) ? 1u : 0u;
+            rank += (q.z > ci || (q.z == ci && j + 2u < i)) ? 1u : 0u;
+            rank += (q.w > ci || (q.w == ci && j + 3u < i)) ? 1u : 0u;
+        }
+        perm[lo + rank] = lo + i;
+    }
+}
+
 static inline bool rv_pow2(uint32_t v) { return v && !(v & (v - 1)); }
 
 // process-wide validation switch; atomic because callers may render from several host threads (one stream each)
@@ -755,12 +849,19 @@ static std::atomic<int> rv_occ_box_enabled{1};
 extern "C" int ngp_render_set_occupied_box(int enabled) { return rv_occ_box_enabled.exchange(enabled ? 1 : 0, std::memory_order_relaxed); }
 static std::atomic<int> rv_block_skip_enabled{1};
 extern "C" int ngp_render_set_block_skip(int enabled) { return rv_block_skip_enabled.exchange(enabled ? 1 : 0, std::memory_order_relaxed); }
+static std::atomic<int> rv_tile_order_enabled{1};
+// validation switch: 0 = every band's tiles in row-major order; results are identical either way
+extern "C" int ngp_render_set_tile_order(int enabled) { return rv_tile_order_enabled.exchange(enabled ? 1 : 0, std::memory_order_relaxed); }
 
 // header: debug words (RV_COUNTERS builds) | extent of the occupied blocks (words 26..31) | band queues (words 32..63)
-static constexpr size_t RV_WS_COARSE = 256, RV_WS_AREA = 256 + 48 * 1024;
+// The coarse map takes at most the LDS left beside the rest of the frame kernel's carve (< 12 KiB), so the end of its 48 KiB region holds the
+// RV_TIMELINE build's histogram (RV_WS_HIST, 8 KiB).
+static constexpr size_t RV_WS_COARSE = 256, RV_WS_HIST = RV_WS_COARSE + 36 * 1024, RV_WS_AREA = 256 + 48 * 1024;
+static_assert(RV_LDS_W + RV_LDS_SH + RV_LDS_LV + RV_LDS_SMP + 36 * 1024 > 160 * 1024, "the coarse map could reach RV_WS_HIST");
+static_assert(RV_WS_HIST + 2048 * sizeof(uint32_t) <= RV_WS_AREA, "workspace carve");
 extern "C" size_t ngp_render_frame_workspace(uint32_t N) {
-    // header | coarse occupancy map (<= 48 KiB) | an area of two u32 per 64 rays: the RV_TIMELINE build's histogram, unused otherwise.  The size
-    // is part of the C ABI (callers allocate it; the cameras of ngp_render_frames_camera follow it), so the area stays reserved.
+    // header | coarse occupancy map (<= 48 KiB) | an area of two u32 per 64 rays: the tile order (queue position -> tile, then each tile's estimated
+    // cost).  The size is part of the C ABI (callers allocate it; the cameras of ngp_render_frames_camera follow it).
     return RV_WS_AREA + 2 * sizeof(uint32_t) * (size_t)ngp_div_up(N, 64u);
 }
 
@@ -815,8 +916,8 @@ static int rv_render_frame(const ngp_field_t* field_host, const float* rays_o, c
 #ifdef RV_COUNTERS
     F.hist = nullptr;
 #ifdef RV_TIMELINE                                      // the timeline's atomics perturb the cycle counters: a build of its own
-    if (workspace_bytes >= RV_WS_AREA + 2048 * sizeof(uint32_t)) {
-        F.hist = reinterpret_cast<uint32_t*>(reinterpret_cast<unsigned char*>(workspace) + RV_WS_AREA);
+    if (workspace_bytes >= RV_WS_HIST + 2048 * sizeof(uint32_t)) {
+        F.hist = reinterpret_cast<uint32_t*>(reinterpret_cast<unsigned char*>(workspace) + RV_WS_HIST);
         if (hipMemsetAsync(F.hist, 0, 2048 * sizeof(uint32_t), s) != hipSuccess) return ngp_fail(NGP_ELAUNCH, "render_frame: memset failed");
     }
 #endif
@@ -827,6 +928,7 @@ static int rv_render_frame(const ngp_field_t* field_host, const float* rays_o, c
 
     // coarse occupancy (needs Morton blocks: H a power of two >= 4) in the workspace, then in LDS
     F.coarse = nullptr; F.coarse_words = 0; F.skip = 0; F.occ_ext = nullptr; F.occ_unit = 0.0f; F.occ_top = 0.0f;
+    F.tile_perm = nullptr;
     static_assert(sizeof(rf_lane_levels) * 4 == RV_LDS_LV, "LDS carve of the level table");
     size_t lds = RV_LDS_W + RV_LDS_SH + RV_LDS_LV + RV_LDS_SMP;
     const void* kernel = reinterpret_cast<const void*>(k_render_frame_multi);
@@ -859,6 +961,19 @@ static int rv_render_frame(const ngp_field_t* field_host, const float* rays_o, c
         // every level's half-width a power of two: H a power of two >= 64, and bound a power of two unless there is one cascade
         int e;
         F.skip = (rv_block_skip_enabled.load(std::memory_order_relaxed) && Hgrid >= 64 && (C == 1 || frexpf(field_host->bound, &e) == 0.5f)) ? 1u : 0u;
+    }
+    // tile order: estimate every tile's cost from the coarse map and sort each band's tiles by it (k_tile_cost, k_tile_sort: the permutation, then
+    // the costs, in the reserved area behind the coarse map)
+    // (not for several frames per launch: their drain is shared by all of them, and the estimate of 8 frames took longer than it saved)
+    const uint32_t n_tiles = F.tile_w ? N / 64u : 0u;
+    if (n_tiles && !F.cams && F.coarse && rv_tile_order_enabled.load(std::memory_order_relaxed) && ngp_div_up(n_tiles, RV_BANDS) <= RV_ORDER_MAX &&
+        workspace_bytes >= RV_WS_AREA + 2 * sizeof(uint32_t) * (size_t)n_tiles) {
+        uint32_t* perm = reinterpret_cast<uint32_t*>(reinterpret_cast<unsigned char*>(workspace) + RV_WS_AREA);
+        uint32_t* cost = perm + n_tiles;
+        hipLaunchKernelGGL(k_tile_cost, dim3(ngp_div_up(n_tiles, 4u)), dim3(256), 0, s, F, P.bound, n_tiles, cost);
+        hipLaunchKernelGGL(k_tile_sort, dim3(RV_BANDS), dim3(1024), 0, s, cost, n_tiles, perm);
+        NGP_CHECK_LAUNCH("render_frame: tile order");
+        F.tile_perm = perm;
     }
     NGP_REQUIRE(lds <= 160 * 1024, "render_frame: LDS carve exceeds 160 KiB");
     // the raised dynamic-LDS limit is a per-device function attribute: set it once on every device this process renders on

@@ -285,7 +285,7 @@ class NGPRenderer(nn.Module):
         return {"image": image.view(H, W, 3), "depth": depth.view(H, W), "weights_sum": weights_sum, "stats": stats}
 
     @torch.no_grad()
-    def render_fused_cameras(self, poses, intrinsics, H, W, dt_gamma=0, bg_color=None, max_steps=1024):
+    def render_fused_cameras(self, poses, intrinsics, H, W, dt_gamma=0, bg_color=None, max_steps=1024, return_workspace=False):
         """P frames in ONE launch (ngp_render_frames_camera): poses [P,4,4] cam2world (tensor, array or nested lists), one set of intrinsics.
         The frame kernel's ramp and drain are paid once per launch instead of once per frame; every pixel equals `render_fused_camera`'s, bit
         for bit.  Returns image [P,H,W,3], depth [P,H,W], weights_sum [P,H*W], stats (summed over the frames)."""
@@ -310,7 +310,10 @@ class NGPRenderer(nn.Module):
                                               _hip.ptr(self.density_bitfield), self.cascade, self.grid_size, dt_gamma, max_steps, bg,
                                               _hip.ptr(image), _hip.ptr(depth), _hip.ptr(weights_sum), _hip.ptr(stats),
                                               _hip.ptr(ws), ws.numel(), _hip.stream()), "render_frames_camera")
-        return {"image": image.view(P, H, W, 3), "depth": depth.view(P, H, W), "weights_sum": weights_sum.view(P, N), "stats": stats}
+        out = {"image": image.view(P, H, W, 3), "depth": depth.view(P, H, W), "weights_sum": weights_sum.view(P, N), "stats": stats}
+        if return_workspace:
+            out["workspace"] = ws
+        return out
 
     # ------------------------------------------------------------------------------------------------------------
     # fixed-step path (nav loop)

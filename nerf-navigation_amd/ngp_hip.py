@@ -99,6 +99,7 @@ _SIGNATURES = {
     "ngp_render_frame_workspace": (c_sz, [c_u32]),
     "ngp_render_set_block_skip": (c_int, [c_int]),
     "ngp_render_set_occupied_box": (c_int, [c_int]),
+    "ngp_render_set_tile_order": (c_int, [c_int]),
     "ngp_field_train_set_two_pass": (c_int, [c_int]),
     "ngp_field_train_set_live_only": (c_int, [c_int]),
     "ngp_render_frame": (c_int, [c_vp, c_vp, c_vp, c_u32, c_u32, c_vp, c_f32, c_vp, c_u32, c_u32, c_f32, c_u32, c_vp,
@@ -229,6 +230,8 @@ def lib():
         if os.environ.get("NGP_OCC_BOX") in ("0", "1"):                  # ... of the march limit at the occupied box (frame kernel and per-op march kernels)
             handle.ngp_render_set_occupied_box(int(os.environ["NGP_OCC_BOX"]))
             handle.ngp_march_set_occupied_box(int(os.environ["NGP_OCC_BOX"]))
+        if os.environ.get("NGP_TILE_ORDER") in ("0", "1"):               # ... of the frame kernel's cost-ordered tiles and bands
+            handle.ngp_render_set_tile_order(int(os.environ["NGP_TILE_ORDER"]))
         if os.environ.get("NGP_FT_LIVE_ONLY") in ("0", "1"):             # ... of the training backward (live samples only | all samples)
             handle.ngp_field_train_set_live_only(int(os.environ["NGP_FT_LIVE_ONLY"]))
     return _lib

@@ -1,6 +1,8 @@
 """Packing / march statistics of one fused 800x800 frame (needs a -DRV_COUNTERS build for rounds and march trips):
-   NGP_HIP_LIB=.../libngp_counters.so python tools/frame_counters.py [res] [--trained STEPS]
---trained STEPS renders a student fitted for STEPS steps to the hand-set scene (bench.py --model trained) instead of the hand-set model."""
+   NGP_HIP_LIB=.../libngp_counters.so python tools/frame_counters.py [res] [--trained STEPS] [--frames P] [--hist-offset BYTES]
+--trained STEPS renders a student fitted for STEPS steps to the hand-set scene (bench.py --model trained) instead of the hand-set model.
+--frames P renders bench's first P orbit poses in ONE launch (ngp_render_frames_camera) instead of one frame.
+--hist-offset: byte offset of the RV_TIMELINE histogram in the workspace (render_fused.hip RV_WS_HIST; before the tile order it was 49408)."""
 import importlib
 import os
 import sys
@@ -18,6 +20,8 @@ from ngp.render import NGPRenderer  # noqa: E402
 dev = torch.device("cuda:0")
 trained = int(sys.argv[sys.argv.index("--trained") + 1]) if "--trained" in sys.argv else 0
 res = int(sys.argv[1]) if len(sys.argv) > 1 and sys.argv[1].isdigit() else 800
+frames = int(sys.argv[sys.argv.index("--frames") + 1]) if "--frames" in sys.argv else 1
+hist_off = int(sys.argv[sys.argv.index("--hist-offset") + 1]) if "--hist-offset" in sys.argv else 256 + 36 * 1024
 model = W.make_model(0)
 field = NGPFieldFF(bound=W.BOUND).to(dev).load_arrays(model)
 ren = NGPRenderer(field, bound=W.BOUND, cuda_ray=True, density_thresh=10.0).to(dev).eval()
@@ -27,11 +31,17 @@ if trained:
     import bench
     ren, fit = bench.fit_model(argparse.Namespace(workload="ring", fit_steps=trained), dev, W, ren)
     print("student:", fit)
-o, d = W.get_rays(W.orbit_pose(1), W.intrinsics(res, res), res, res)
-o, d = torch.from_numpy(o).to(dev), torch.from_numpy(d).to(dev)
+if frames > 1:
+    poses = np.stack([W.orbit_pose(k) for k in range(frames)]).astype(np.float32)
+    intr = W.intrinsics(res, res)
+    run = lambda **kw: ren.render_fused_cameras(poses, intr, res, res, bg_color=1, **kw)  # noqa: E731
+else:
+    o, d = W.get_rays(W.orbit_pose(1), W.intrinsics(res, res), res, res)
+    o, d = torch.from_numpy(o).to(dev), torch.from_numpy(d).to(dev)
+    run = lambda **kw: ren.render_fused(o[None], d[None], bg_color=1, image_width=res, **kw)  # noqa: E731
 for _ in range(3):                                      # warm-up launches: the counters below are those of a warm frame
-    ren.render_fused(o[None], d[None], bg_color=1, image_width=res)
-out = ren.render_fused(o[None], d[None], bg_color=1, image_width=res, return_workspace=True)
+    run()
+out = run(return_workspace=True)
 torch.cuda.synchronize()
 st = out["stats"].cpu().numpy().astype(np.int64)
 ws = out["workspace"][:128].view(torch.int32).cpu().numpy().astype(np.int64)
@@ -48,7 +58,7 @@ if ws[1]:
         float(c[0]) / nw / 1e6, float(c[1]) / nw / 1e6, float(c[2]) / nw / 1e6, float(c[3]) / nw / 1e6, float(c[4]) / nw / 1e6,
         float(c[5]) / 1e6, cmin / 1e6))
     # timeline (-DRV_COUNTERS -DRV_TIMELINE build; its atomics perturb the cycle counters above): 20 us bins of samples / wave-rounds / live lanes at round start / waves finishing
-    off = 256 + 48 * 1024
+    off = hist_off
     if out["workspace"].numel() >= off + 4 * 2048:
         h = out["workspace"][off:off + 4 * 2048].view(torch.int32).cpu().numpy().astype(np.int64).reshape(4, 512)
         last = int(np.nonzero(h[1])[0].max()) + 1 if h[1].any() else 0
@@ -59,3 +69,10 @@ if ws[1]:
             smp, rnd, live, f = (int(h[k, b:b + step].sum()) for k in range(4))
             fin += f
             print("  %5d  %6.2f  %6d  %5.1f  %6.1f  %5d" % (20 * b, smp / (20e-6 * step) / 1e9, rnd, live / max(rnd, 1), smp / max(rnd, 1), fin))
+        # ramp = until the 20 us rate first reaches 90 % of the median rate of the frame's middle half; first retire = first bin in which a wave finished
+        rate = h[0, :last].astype(np.float64)
+        mid = float(np.median(rate[last // 4: 3 * last // 4])) if last >= 4 else 0.0
+        ramp = int(np.argmax(rate >= 0.9 * mid)) if mid > 0 else 0
+        first = int(np.nonzero(h[3, :last + 1])[0].min()) if h[3].any() else last
+        print("summary: frame %d us, ramp %d us (%.1f %%), first wave retires at %d us (%.1f %% of the frame), steady %.2f G samples/s" % (
+            20 * last, 20 * ramp, 100.0 * ramp / max(last, 1), 20 * first, 100.0 * first / max(last, 1), mid / 20e-6 / 1e9))
