@@ -561,6 +561,43 @@ int ngp_marching_cubes_emit(const float* u, uint32_t X, uint32_t Y, uint32_t Z, 
 /* The 256-case table (256 rows of NGP_MC_TABLE_ROW bytes) copied to a host buffer; touches no device. */
 int ngp_marching_cubes_table(uint8_t* table_host, size_t bytes);
 
+/* ------------------------------------------------------------------------ */
+/* Trajectory planner  (reference: Planner, nav/quad_plot.py:120-290;       */
+/* csrc/nav_plan.hip, DESIGN.md §3.5 "Native planner")                     */
+/* ------------------------------------------------------------------------ */
+
+/* R = rows of states [R,4] (x, y, z, heading), 2 <= R <= 255; S = R + 3 trajectory rows; B body points, 1 <= B <= 65536;
+ * P = 4 R + 2 parameters in torch's order: initial_accel [2], then states [R,4] row-major. */
+typedef struct {
+    float dt;                    /* T_final / steps */
+    float g, mass;
+    float J[9];                  /* inertia, row-major */
+    float start[18], end[18];    /* full states: pos, vel, rotation (row-major), omega */
+    float rot[9];                /* row-major axis change applied to the world points before the field: x @ rot (simulate.py:340) */
+    int32_t fade_out_epoch;
+    float fade_out_sharpness;
+    double lr, beta1, beta2, eps; /* torch.optim.Adam(capturable=True); rounded to float32 as torch does */
+} ngp_plan_cfg_t;
+
+/* Adam state, device float32: exp_avg [P], exp_avg_sq [P], grad [P] (the gradient of the last epoch), step [1]; zero it to restart. */
+#define NGP_PLAN_ADAM_FLOATS(R) (3u * (4u * (R) + 2u) + 1u)
+
+/* bytes of the workspace of ngp_plan_epochs: world points [S*B,3], sigma [S*B], jacobian [S*B,3]; 0 outside the supported R, B */
+size_t ngp_plan_workspace(uint32_t R, uint32_t B);
+/* calc_everything forward (nav/quad_plot.py:120-196), one launch: full_states [S,18] (get_full_states), actions [S,4] (get_actions),
+ * points [S*B,3] (body_to_world of body [B,3]); any output may be NULL (body and B only matter with points). */
+int ngp_plan_kinematics(const ngp_plan_cfg_t* cfg_host, const float* states, const float* initial_accel, uint32_t R,
+                        const float* body, uint32_t B, float* full_states, float* actions, float* points, void* stream);
+/* n_epochs epochs of Planner.learn_init / learn_update: per epoch the kinematics, ngp_nav_density_value_jac over the world points
+ * and the cost step, 3 launches on `stream`, no synchronisation.  Epoch k has index first_epoch + k (the fade-out mask); losses [k]
+ * (may be NULL) is total_cost() before its step.  per_state (may be NULL): [2,S] = per-state cost, collision * 1e6 of the last epoch.
+ * update = 1: Adam step on states and initial_accel in place; update = 0: cost and gradient only (adam_state's grad slot).
+ * Deterministic: two runs are bit-identical. */
+int ngp_plan_epochs(const ngp_nav_field_t* field_host, const void* prepared, const ngp_plan_cfg_t* cfg_host,
+                    float* states, float* initial_accel, float* adam_state, const float* body, uint32_t B, uint32_t R,
+                    uint32_t first_epoch, uint32_t n_epochs, int update, float* losses, float* per_state,
+                    void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

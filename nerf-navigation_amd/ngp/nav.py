@@ -374,3 +374,234 @@ class NativeNavQueries(NavQueries):
                 images.append(img)
                 depths.append(dep)
         return {"image": torch.cat(images).view(B, N, 3), "depth": torch.cat(depths).view(B, N)}
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# the planner's optimisation loop on the device (csrc/nav_plan.hip): three launches per epoch, no host synchronisation
+# ------------------------------------------------------------------------------------------------------------------------
+def _reduced_state(state):
+    """Planner.full_to_reduced_state (nav/quad_plot.py:55-62): 18-vector -> (x, y, z, heading)"""
+    R = state[6:15].reshape(3, 3)
+    return torch.cat([state[:3], torch.atan2(R[1, 0], R[0, 0])[None]]).detach()
+
+
+class NativePlanner:
+    """Planner (nav/quad_plot.py) with its optimisation loop native: calc_everything -> body_to_world -> get_state_cost -> total_cost ->
+    backward -> Adam run as ngp_plan_epochs, i.e. per epoch one launch of the kinematics, one of the density query (NativeNavQueries'
+    value-and-Jacobian kernel, simulate.py:340's axis change folded in) and one of cost, gradient and Adam step.  Same cfg keys, the same
+    semantics as the reference's methods; the loss history is a device tensor (`losses`) instead of a print per epoch.
+
+        traj.a_star_init()
+        plan = NativePlanner.from_planner(traj, queries)      # queries: NativeNavQueries
+        plan.learn_init()
+    """
+    SAVE_STEP = 50                                          # learn_init / learn_update save every 50th epoch when `basefolder` is set
+
+    def __init__(self, start_state, end_state, cfg, queries):
+        self._bind(queries)
+        self._set_cfg(cfg)
+        self.start_state = start_state.detach().to(self.device, torch.float32)
+        self.end_state = end_state.detach().to(self.device, torch.float32)
+        slider = torch.linspace(0, 1, self.steps)[1:-1, None]
+        states = (1 - slider) * _reduced_state(self.start_state.cpu()) + slider * _reduced_state(self.end_state.cpu())
+        self.states = states.to(self.device).contiguous()
+        self.initial_accel = torch.tensor([cfg["g"], cfg["g"]], dtype=torch.float32, device=self.device)
+        ext = torch.as_tensor(cfg["body"], dtype=torch.float32)
+        nb = [int(v) for v in cfg["nbins"]]
+        axes = [torch.linspace(float(ext[k, 0]), float(ext[k, 1]), nb[k]) for k in range(3)]
+        self.robot_body = torch.stack(torch.meshgrid(*axes, indexing="ij"), dim=-1).reshape(-1, 3).to(self.device).contiguous()
+        self.epoch = 0
+        self.losses = torch.empty(0, device=self.device)
+
+    @classmethod
+    def from_planner(cls, planner, queries):
+        """adopt a reference Planner (after its own a_star_init()): start / end, cfg, states, initial_accel, robot_body"""
+        self = cls.__new__(cls)
+        self._bind(queries)
+        self._set_cfg(planner.cfg)
+        self.start_state = planner.start_state.detach().to(self.device, torch.float32)
+        self.end_state = planner.end_state.detach().to(self.device, torch.float32)
+        self.states = planner.states.detach().to(self.device, torch.float32).contiguous().clone()
+        self.initial_accel = planner.initial_accel.detach().to(self.device, torch.float32).contiguous().clone()
+        self.robot_body = planner.robot_body.detach().to(self.device, torch.float32).contiguous().clone()
+        self.epoch = int(getattr(planner, "epoch", 0))
+        self.losses = torch.empty(0, device=self.device)
+        if hasattr(planner, "basefolder"):
+            self.basefolder = planner.basefolder
+        return self
+
+    def store_into(self, planner):
+        """write states / initial_accel (leaf tensors with requires_grad, as the reference keeps them), start_state and epoch back into a
+        reference Planner, so that its save_poses / plot see the native result"""
+        planner.states = self.states.detach().clone().requires_grad_(True)
+        planner.initial_accel = self.initial_accel.detach().clone().requires_grad_(True)
+        planner.start_state = self.start_state
+        planner.epoch = self.epoch
+        return planner
+
+    # -- plumbing ------------------------------------------------------------------------------------------------------
+    def _bind(self, queries):
+        if not isinstance(queries, NativeNavQueries):
+            raise ValueError(f"NativePlanner needs a NativeNavQueries (the fused float32 queries), got {type(queries).__name__}")
+        self.queries = queries
+        self.device = queries.native.field.encoder.embeddings.device
+        self._ws = None
+
+    def _set_cfg(self, cfg):
+        self.cfg = cfg
+        self.T_final, self.steps, self.lr = cfg["T_final"], int(cfg["steps"]), cfg["lr"]
+        self.epochs_init, self.epochs_update = int(cfg["epochs_init"]), int(cfg["epochs_update"])
+        self.fade_out_epoch, self.fade_out_sharpness = int(cfg["fade_out_epoch"]), cfg["fade_out_sharpness"]
+        self.mass, self.J, self.g = cfg["mass"], cfg["I"], cfg["g"]
+        self.dt = self.T_final / self.steps
+
+    def _cfg_struct(self):
+        import ngp_hip as _hip
+        c = _hip.ngp_plan_cfg_t()
+        c.dt, c.g, c.mass = self.dt, float(self.g), float(self.mass)
+        c.J[:] = [float(v) for v in torch.as_tensor(self.J, dtype=torch.float32).reshape(-1).tolist()]
+        c.start[:] = [float(v) for v in self.start_state.cpu().tolist()]
+        c.end[:] = [float(v) for v in self.end_state.cpu().tolist()]
+        c.rot[:] = list(NativeNavQueries._ROT9)
+        c.fade_out_epoch, c.fade_out_sharpness = self.fade_out_epoch, float(self.fade_out_sharpness)
+        c.lr, c.beta1, c.beta2, c.eps = float(self.lr), 0.9, 0.999, 1e-8
+        return c
+
+    @property
+    def R(self):
+        return int(self.states.shape[0])
+
+    @property
+    def S(self):
+        return self.R + 3
+
+    def _workspace(self):
+        import ngp_hip as _hip
+        nbytes = _hip.lib().ngp_plan_workspace(self.R, int(self.robot_body.shape[0]))
+        if self._ws is None or self._ws.numel() < nbytes:
+            self._ws = _hip.workspace(nbytes, self.device)
+        return self._ws
+
+    def new_adam_state(self):
+        """zeroed Adam moments and step: the reference builds a new optimiser in every learn_init / learn_update"""
+        import ngp_hip as _hip
+        return torch.zeros(_hip.plan_adam_floats(self.R), dtype=torch.float32, device=self.device)
+
+    def run_epochs(self, first_epoch, n_epochs, adam_state, update=True, losses=None, per_state=None):
+        """queue n_epochs epochs (3 launches each) on the current stream; no synchronisation.  losses: [n_epochs] device tensor or None;
+        per_state: [2, S] (per-state cost, collision) of the last epoch or None"""
+        import ctypes
+        import ngp_hip as _hip
+        st, prep = self.queries.native.struct()
+        ws = self._workspace()
+        c = self._cfg_struct()
+        _hip.check(_hip.lib().ngp_plan_epochs(ctypes.byref(st), _hip.ptr(prep), ctypes.byref(c), _hip.ptr(self.states), _hip.ptr(self.initial_accel),
+                                              _hip.ptr(adam_state), _hip.ptr(self.robot_body), int(self.robot_body.shape[0]), self.R, int(first_epoch),
+                                              int(n_epochs), 1 if update else 0, _hip.ptr(losses), _hip.ptr(per_state), _hip.ptr(ws), ws.numel(),
+                                              _hip.stream()), "plan_epochs")
+
+    def _kinematics(self, with_points=False):
+        import ctypes
+        import ngp_hip as _hip
+        S, B = self.S, int(self.robot_body.shape[0])
+        full = torch.empty(S, 18, dtype=torch.float32, device=self.device)
+        actions = torch.empty(S, 4, dtype=torch.float32, device=self.device)
+        points = torch.empty(S, B, 3, dtype=torch.float32, device=self.device) if with_points else None
+        c = self._cfg_struct()
+        _hip.check(_hip.lib().ngp_plan_kinematics(ctypes.byref(c), _hip.ptr(self.states), _hip.ptr(self.initial_accel), self.R,
+                                                  _hip.ptr(self.robot_body), B, _hip.ptr(full), _hip.ptr(actions), _hip.ptr(points),
+                                                  _hip.stream()), "plan_kinematics")
+        return full, actions, points
+
+    # -- the reference's interface ---------------------------------------------------------------------------------------
+    def get_full_states(self):
+        return self._kinematics()[0]
+
+    def get_actions(self):
+        return self._kinematics()[1]
+
+    def get_next_action(self):
+        return self.get_actions()[0, :]
+
+    def body_to_world(self):
+        """the world points [S,B,3] of the body at every state"""
+        return self._kinematics(with_points=True)[2]
+
+    def cost_and_gradient(self, epoch=None):
+        """get_state_cost + total_cost().backward() at the current parameters and `epoch` (default self.epoch): dict(total, per_state, collision,
+        grad_initial_accel [2], grad_states [R,4]), device tensors"""
+        adam = self.new_adam_state()
+        loss = torch.empty(1, dtype=torch.float32, device=self.device)
+        ps = torch.empty(2, self.S, dtype=torch.float32, device=self.device)
+        self.run_epochs(self.epoch if epoch is None else epoch, 1, adam, update=False, losses=loss, per_state=ps)
+        P = 4 * self.R + 2
+        grad = adam[2 * P:3 * P]
+        return dict(total=loss[0], per_state=ps[0], collision=ps[1], grad_initial_accel=grad[:2], grad_states=grad[2:].view(self.R, 4))
+
+    def get_state_cost(self):
+        res = self.cost_and_gradient()
+        return res["per_state"], res["collision"]
+
+    def total_cost(self):
+        return self.cost_and_gradient()["total"]
+
+    def _learn(self, n, folder_tag, name):
+        adam = self.new_adam_state()
+        self.losses = torch.empty(n, dtype=torch.float32, device=self.device)
+        base = getattr(self, "basefolder", None)
+        if base is None:
+            if n:
+                self.run_epochs(0, n, adam, losses=self.losses)
+            self.epoch = max(n - 1, 0)
+            return self.losses
+        head = 0
+        while head < n:                                     # the reference saves after the step of every epoch it % 50 == 0
+            tail = min(n, head + 1 if head == 0 else head + self.SAVE_STEP)
+            self.run_epochs(head, tail - head, adam, losses=self.losses[head:])
+            it = tail - 1
+            self.epoch = it
+            if it % self.SAVE_STEP == 0:
+                self.save_poses(base / f"{folder_tag}_poses" / name(it // self.SAVE_STEP))
+                self.save_costs(base / f"{folder_tag}_costs" / name(it // self.SAVE_STEP))
+            head = tail
+        return self.losses
+
+    def learn_init(self):
+        """Planner.learn_init: epochs_init epochs from fresh Adam moments"""
+        return self._learn(self.epochs_init, "init", lambda k: f"{k}.json")
+
+    def learn_update(self, iteration):
+        """Planner.learn_update: epochs_update epochs from fresh Adam moments"""
+        return self._learn(self.epochs_update, "replan", lambda k: f"{k}_time{iteration}.json")
+
+    def update_state(self, measured_state):
+        """Planner.update_state: the measured state becomes the start, states[0] is dropped, initial_accel = actions[1:3, 0]"""
+        actions = self.get_actions()
+        self.start_state = measured_state.detach().to(self.device, torch.float32)
+        self.states = self.states[1:, :].contiguous().clone()
+        self.initial_accel = actions[1:3, 0].contiguous().clone()
+
+    def save_poses(self, filename):
+        """Planner.save_poses: {"poses": S 4 x 4 matrices}"""
+        import json
+        full = self.get_full_states().cpu().numpy().astype("float64")
+        poses = []
+        for row in full:
+            pose = [[0.0] * 4 for _ in range(4)]
+            for a in range(3):
+                pose[a][:3] = [float(v) for v in row[6 + 3 * a:9 + 3 * a]]
+                pose[a][3] = float(row[a])
+            pose[3][3] = 1.0
+            poses.append(pose)
+        with open(filename, "w+") as f:
+            json.dump({"poses": poses}, f, indent=4)
+
+    def save_costs(self, filename):
+        """Planner.save_costs: colision_loss, pos, actions, total_cost (the reference's keys)"""
+        import json
+        full, actions, _ = self._kinematics()
+        res = self.cost_and_gradient()
+        out = {"colision_loss": res["collision"].cpu().tolist(), "pos": full[:, :3].cpu().tolist(), "actions": actions.cpu().tolist(),
+               "total_cost": res["per_state"].cpu().tolist()}
+        with open(filename, "w+") as f:
+            json.dump(out, f, indent=4)

@@ -123,6 +123,9 @@ _SIGNATURES = {
     "ngp_marching_cubes_count": (c_int, [c_vp, c_u32, c_u32, c_u32, c_f32, c_vp, c_sz, c_vp, c_vp, c_vp]),
     "ngp_marching_cubes_emit": (c_int, [c_vp, c_u32, c_u32, c_u32, c_f32, c_vp, c_sz, c_vp, c_u64, c_vp, c_u64, c_vp]),
     "ngp_marching_cubes_table": (c_int, [c_vp, c_sz]),
+    "ngp_plan_workspace": (c_sz, [c_u32, c_u32]),
+    "ngp_plan_kinematics": (c_int, [c_vp, c_vp, c_vp, c_u32, c_vp, c_u32, c_vp, c_vp, c_vp, c_vp]),
+    "ngp_plan_epochs": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_u32, c_u32, c_u32, c_u32, c_int, c_vp, c_vp, c_vp, c_sz, c_vp]),
 }
 
 EXPORTS = tuple(_SIGNATURES)
@@ -154,6 +157,18 @@ class ngp_nav_field_t(ctypes.Structure):
     """include/ngp_hip.h: ngp_nav_field_t"""
     _fields_ = [("embeddings", c_vp), ("offsets_host", c_vp), ("sigma_w0", c_vp), ("sigma_w1", c_vp), ("color_w0", c_vp), ("color_w1", c_vp),
                 ("color_w2", c_vp), ("L", c_u32), ("H", c_u32), ("S", c_f32), ("bound", c_f32), ("density_scale", c_f32)]
+
+
+class ngp_plan_cfg_t(ctypes.Structure):
+    """include/ngp_hip.h: ngp_plan_cfg_t"""
+    _fields_ = [("dt", c_f32), ("g", c_f32), ("mass", c_f32), ("J", c_f32 * 9), ("start", c_f32 * 18), ("end", c_f32 * 18), ("rot", c_f32 * 9),
+                ("fade_out_epoch", ctypes.c_int32), ("fade_out_sharpness", c_f32), ("lr", ctypes.c_double), ("beta1", ctypes.c_double),
+                ("beta2", ctypes.c_double), ("eps", ctypes.c_double)]
+
+
+def plan_adam_floats(R):
+    """include/ngp_hip.h: NGP_PLAN_ADAM_FLOATS(R)"""
+    return 3 * (4 * int(R) + 2) + 1
 
 
 def build(verbose=False):
