@@ -438,7 +438,10 @@ int ngp_field_train_live_list(void* workspace, uint32_t M, const uint32_t** list
  * image_width: when rays_o/rays_d are a row-major image (width and height multiples of 8) pass its width and the
  * kernel walks the rays in 8x8 pixel tiles for cache locality; 0 = rays in no particular order.  Results do not
  * depend on it.
- * workspace: ngp_render_frame_workspace(N) bytes. */
+ * workspace: ngp_render_frame_workspace(N) bytes; at least 256 (NGP_EINVAL below that).  A caller that passes less than the full size gets the same
+ * frame by a slower route: without the tile order below 256 + 48 KiB + 8 bytes per 64 rays, without the coarse occupancy map below 256 + C * Hgrid^3 / 512.
+ * Hgrid (and H of ngp_march_rays / ngp_march_rays_train): a power of two, NGP_EINVAL otherwise (cells are addressed by Morton index, which for
+ * any other size runs beyond the bitfield's C * H^3 bits). */
 size_t ngp_render_frame_workspace(uint32_t N);
 /* Validation switch, process-wide, default 1: ngp_render_frame jumps through empty 4^3 / 16^3 blocks of the occupancy
  * grid when that provably visits the reference's samples (render_fused.hip, rv_probe).  0 = march cell by cell like

@@ -672,6 +672,7 @@ static int rm_march_rays_train(const float* rays_o, const float* rays_d, const u
     }
     NGP_REQUIRE(rays_o && rays_d && grid && nears && fars && xyzs && dirs && deltas && rays && counter, "march_rays_train: null pointer");
     NGP_REQUIRE(C >= 1 && C <= 16 && H >= 1 && H <= 1024 && max_steps >= 1, "march_rays_train: bad C/H/max_steps");
+    NGP_REQUIRE((H & (H - 1u)) == 0u, "march_rays_train: the grid size must be a power of two (cells are addressed by Morton index: beyond H^3 otherwise)");
     NGP_REQUIRE(workspace && workspace_bytes >= ngp_march_rays_train_workspace(N), "march_rays_train: workspace too small");
     if (N == 0) return NGP_OK;
     const uint32_t nblocks = ngp_div_up(N, RM_RAY_BLOCK);
@@ -1252,6 +1253,7 @@ static int march_rays_launch(bool fill, uint32_t M, uint32_t n_alive, uint32_t n
     if ((n_alive == 0 || n_step == 0) && !(fill && M)) return NGP_OK;
     NGP_REQUIRE(rays_alive && rays_t && rays_o && rays_d && grid && nears && fars && xyzs && dirs && deltas, "march_rays: null pointer");
     NGP_REQUIRE(C >= 1 && C <= 16 && H >= 1 && H <= 1024 && max_steps >= 1, "march_rays: bad C/H/max_steps");
+    NGP_REQUIRE((H & (H - 1u)) == 0u, "march_rays: the grid size must be a power of two (cells are addressed by Morton index: beyond H^3 otherwise)");
     NGP_REQUIRE(!fill || (uint64_t)M >= (uint64_t)n_alive * n_step, "march_rays: M is smaller than n_alive * n_step");
     march_args a{rays_o, rays_d, grid, nears, fars, bound, dt_gamma, max_steps, 0u, C, H, M, perturb};
     // the coarse map pays when rays cross empty space; it is rebuilt on every call (2 us: the bitfield may have changed, and a cache

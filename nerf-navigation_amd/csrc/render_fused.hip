@@ -890,6 +890,9 @@ static int rv_render_frame(const ngp_field_t* field_host, const float* rays_o, c
     NGP_REQUIRE(stats && workspace && workspace_bytes >= RV_WS_COARSE, "render_frame: stats / workspace missing");
     NGP_REQUIRE(aabb_host && bg_color3_host, "render_frame: aabb / bg_color are host pointers and must not be null");
     NGP_REQUIRE(C >= 1 && C <= 16 && Hgrid >= 1 && Hgrid <= 1024 && max_steps >= 1, "render_frame: bad C/H/max_steps");
+    // cells are addressed by Morton index: for a grid size that is not a power of two the index of a cell can lie beyond H^3 (H = 48: cell (47, 47, 47) has
+    // index 2^18 - 1 > 48^3), i.e. beyond the end of the bitfield
+    NGP_REQUIRE(rv_pow2(Hgrid), "render_frame: the grid size must be a power of two (cells are addressed by Morton index)");
     hipStream_t s = (hipStream_t)stream;
     if (hipMemsetAsync(stats, 0, 4 * sizeof(uint32_t), s) != hipSuccess || hipMemsetAsync(workspace, 0, RV_WS_COARSE, s) != hipSuccess)
         return ngp_fail(NGP_ELAUNCH, "render_frame: memset failed");

@@ -211,6 +211,20 @@ def orbit_pose(k, n=8, radius=1.6, height=0.6):
     return pose.astype(np.float32)
 
 
+def look_pose(eye, forward):
+    """Camera-to-world [4,4] float32 of a camera at `eye` looking along `forward` (any length), z up; camera axes as `orbit_pose`
+    builds them (+z forward, +x right, +y down).  Looking straight up or down, where z cannot be the up vector, +y is."""
+    eye = np.asarray(eye, np.float64)
+    fwd = np.asarray(forward, np.float64)
+    fwd = fwd / np.linalg.norm(fwd)
+    up = np.array([0.0, 0.0, 1.0]) if abs(fwd[2]) < 0.999 else np.array([0.0, 1.0, 0.0])
+    right = np.cross(fwd, up); right /= np.linalg.norm(right)
+    down = np.cross(fwd, right)
+    pose = np.eye(4)
+    pose[:3, 0], pose[:3, 1], pose[:3, 2], pose[:3, 3] = right, down, fwd, eye
+    return pose.astype(np.float32)
+
+
 def get_rays(pose, intr, H, W):
     """get_rays for a full image (nerf/utils.py:53-116, N = -1 branch), float32 numpy: rays_o, rays_d [H*W, 3]."""
     fx, fy, cx, cy = (np.float32(v) for v in intr)

@@ -101,3 +101,45 @@ def linear_field_from_model(model, dev):
             assert tuple(layer.weight.shape) == w.shape, (layer.weight.shape, w.shape)
             layer.weight.copy_(torch.from_numpy(np.ascontiguousarray(w)))
     return field
+
+
+# the frame kernel's workspace carve (render_fused.hip: RV_WS_COARSE, RV_WS_AREA; restated, the size is part of the C ABI): the header, and the end of the
+# region of the coarse occupancy map, behind which two u32 per 64 rays hold the tile order
+FRAME_WS_HEADER = 256
+FRAME_WS_AREA = 256 + 48 * 1024
+
+
+def render_frame(ren, o, d, width, *, tile_order=None, block_skip=None, occupied_box=None, dt_gamma=0.0, min_near=None, max_steps=1024,
+                 bitfield=None, workspace_bytes=None, grid_size=None):
+    """ngp_render_frame as NGPRenderer.render_fused calls it, through ctypes, with NaN-filled outputs and a 0xAB-filled workspace, so that a value the
+    kernel did not write, or a workspace word it relied on without writing it, shows.  The three process-wide switches are set when given (0 / 1) and
+    restored afterwards; `bitfield` replaces the renderer's (same cascades and grid size), `workspace_bytes` the size ngp_render_frame_workspace
+    asks for, `min_near` and `grid_size` the renderer's.  Returns (outputs, workspace, return code); the outputs stay NaN / -1 when the call refuses."""
+    import ctypes
+
+    import ngp_hip as H
+    import torch
+    L = H.lib()
+    N, dev = o.shape[0], o.device
+    image = torch.full((N, 3), float("nan"), device=dev)
+    depth = torch.full((N,), float("nan"), device=dev)
+    weights_sum = torch.full((N,), float("nan"), device=dev)
+    stats = torch.full((4,), -1, dtype=torch.int32, device=dev)
+    ws_bytes = L.ngp_render_frame_workspace(N) if workspace_bytes is None else int(workspace_bytes)
+    ws = torch.full((max(ws_bytes, 16),), 0xAB, dtype=torch.uint8, device=dev)
+    bg = (ctypes.c_float * 3)(1.0, 1.0, 1.0)
+    aabb = (ctypes.c_float * 6)(*[float(v) for v in ren._aabb().tolist()])
+    f = ren.field.fused_state(ren.density_scale)
+    bits = ren.density_bitfield if bitfield is None else bitfield
+    assert bits.numel() == ren.density_bitfield.numel() and bits.dtype == torch.uint8 and bits.is_contiguous()
+    setters = ((L.ngp_render_set_tile_order, tile_order), (L.ngp_render_set_block_skip, block_skip), (L.ngp_render_set_occupied_box, occupied_box))
+    previous = [(fn, fn(int(value))) for fn, value in setters if value is not None]
+    try:
+        rc = L.ngp_render_frame(ctypes.byref(f), H.ptr(o), H.ptr(d), N, int(width), aabb, ren.min_near if min_near is None else float(min_near),
+                                H.ptr(bits), ren.cascade, ren.grid_size if grid_size is None else int(grid_size), float(dt_gamma), int(max_steps), bg,
+                                H.ptr(image), H.ptr(depth), H.ptr(weights_sum), H.ptr(stats), H.ptr(ws), ws_bytes, H.stream())
+        torch.cuda.synchronize()
+    finally:
+        for fn, value in previous:
+            fn(value)
+    return dict(image=image, depth=depth, weights_sum=weights_sum, stats=stats), ws, rc

@@ -2,16 +2,15 @@
 (render_fused.hip: k_tile_cost, k_tile_sort).  The order changes when a ray is rendered, never what it computes: with the switch on and off,
 images, depths, weights and statistics are bit-identical, every pixel is written, and the order read back from the workspace is a permutation
 of each band's tiles."""
-import ctypes
-
 import numpy as np
 import pytest
 import torch
 
+from _util import FRAME_WS_AREA as WS_AREA, render_frame  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 
 BANDS = 32
-WS_AREA = 256 + 48 * 1024
 
 
 @pytest.fixture(scope="module")
@@ -33,25 +32,9 @@ def scene(dev):
 def _render(ren, o, d, width, order):
     """ngp_render_frame as NGPRenderer.render_fused calls it, with NaN-filled outputs; returns the outputs and the workspace."""
     import ngp_hip as H
-    L = H.lib()
-    N, dev = o.shape[0], o.device
-    image = torch.full((N, 3), float("nan"), device=dev)
-    depth = torch.full((N,), float("nan"), device=dev)
-    weights_sum = torch.full((N,), float("nan"), device=dev)
-    stats = torch.full((4,), -1, dtype=torch.int32, device=dev)
-    ws = torch.full((L.ngp_render_frame_workspace(N),), 0xAB, dtype=torch.uint8, device=dev)
-    bg = (ctypes.c_float * 3)(1.0, 1.0, 1.0)
-    aabb = (ctypes.c_float * 6)(*[float(v) for v in ren._aabb().tolist()])
-    f = ren.field.fused_state(ren.density_scale)
-    previous = L.ngp_render_set_tile_order(order)
-    try:
-        H.check(L.ngp_render_frame(ctypes.byref(f), H.ptr(o), H.ptr(d), N, int(width), aabb, ren.min_near, H.ptr(ren.density_bitfield),
-                                   ren.cascade, ren.grid_size, 0.0, 1024, bg, H.ptr(image), H.ptr(depth), H.ptr(weights_sum), H.ptr(stats),
-                                   H.ptr(ws), ws.numel(), H.stream()), "render_frame")
-        torch.cuda.synchronize()
-    finally:
-        L.ngp_render_set_tile_order(previous)
-    return dict(image=image, depth=depth, weights_sum=weights_sum, stats=stats), ws
+    out, ws, rc = render_frame(ren, o, d, width, tile_order=order)
+    H.check(rc, "render_frame")
+    return out, ws
 
 
 def _check(ren, W, pose, res, dev, width=None):
