@@ -282,28 +282,14 @@ extern "C" uint32_t ngp_density_grid_points(uint32_t cascade, uint32_t H, int pa
     return (uint32_t)(partial ? cascade * 2u * (H3 / 4u) : cascade * H3);
 }
 
-// workspace layout: tmp grid [cascade H^3] f32 | occupied-cell lists [cascade H^3] u32 | block sums / partial means | n_occ, thresh
-extern "C" size_t ngp_density_grid_workspace(uint32_t cascade, uint32_t H) {
+// workspace layout: tmp grid [cascade H^3] f32 | occupied-cell lists [cascade H^3] u32 | block sums / partial means | n_occ (64 B), thresh
+struct dg_ws { float* tmp; uint32_t* occ; double* partial; uint32_t* n_occ; float* thresh; size_t total; };
+static inline dg_ws dg_layout(uint32_t cascade, uint32_t H, void* base) {
     const size_t n = (size_t)cascade * H * H * H;
-    const size_t nblocks = (n + DG_BLOCK - 1) / DG_BLOCK;
-    return n * 4 + n * 4 + nblocks * 8 + 256;
+    ngp_carver c(base);
+    return {c.take<float>(n, 1), c.take<uint32_t>(n, 1), c.take<double>((n + DG_BLOCK - 1) / DG_BLOCK, 1), c.take<uint32_t>(16, 1), c.take<float>(48, 1), c.total()};
 }
-
-struct dg_ws {
-    float* tmp; uint32_t* occ; double* partial; uint32_t* block_sums; uint32_t* n_occ; float* thresh;
-};
-static inline dg_ws dg_carve(void* workspace, uint32_t cascade, uint32_t H) {
-    const size_t n = (size_t)cascade * H * H * H;
-    const size_t nblocks = (n + DG_BLOCK - 1) / DG_BLOCK;
-    char* p = (char*)workspace;
-    dg_ws w;
-    w.tmp = (float*)p; p += n * 4;
-    w.occ = (uint32_t*)p; p += n * 4;
-    w.partial = (double*)p; w.block_sums = (uint32_t*)p; p += nblocks * 8;         // never live at the same time
-    w.n_occ = (uint32_t*)p; p += 64;
-    w.thresh = (float*)p;
-    return w;
-}
+extern "C" size_t ngp_density_grid_workspace(uint32_t cascade, uint32_t H) { return dg_layout(cascade, H, nullptr).total; }
 
 extern "C" int ngp_density_grid_sample(const float* density_grid, uint32_t cascade, uint32_t H, float bound, int partial, uint64_t seed,
                                        uint64_t iteration, float* xyzs, int32_t* cells, void* workspace, size_t workspace_bytes,
@@ -319,12 +305,13 @@ extern "C" int ngp_density_grid_sample(const float* density_grid, uint32_t casca
         return NGP_OK;
     }
     NGP_REQUIRE(density_grid && cells, "density_grid_sample: the partial sweep needs density_grid and cells");
-    NGP_REQUIRE(workspace && workspace_bytes >= ngp_density_grid_workspace(cascade, H), "density_grid_sample: workspace too small");
-    const dg_ws w = dg_carve(workspace, cascade, H);
+    const dg_ws w = dg_layout(cascade, H, workspace);
+    NGP_REQUIRE(workspace && workspace_bytes >= w.total, "density_grid_sample: workspace too small");
     const uint32_t nblocks = n / DG_BLOCK, N = H3 / 4;
-    hipLaunchKernelGGL(k_dg_occ_count, dim3(nblocks), dim3(DG_BLOCK), 0, s, density_grid, n, w.block_sums);
-    hipLaunchKernelGGL(k_dg_occ_scan, dim3(1), dim3(DG_BLOCK), 0, s, w.block_sums, H3 / DG_BLOCK, cascade, w.n_occ);
-    hipLaunchKernelGGL(k_dg_occ_write, dim3(nblocks), dim3(DG_BLOCK), 0, s, density_grid, n, H3, w.block_sums, w.occ);
+    uint32_t* block_sums = reinterpret_cast<uint32_t*>(w.partial);                  // the update's partial means: never live at the same time
+    hipLaunchKernelGGL(k_dg_occ_count, dim3(nblocks), dim3(DG_BLOCK), 0, s, density_grid, n, block_sums);
+    hipLaunchKernelGGL(k_dg_occ_scan, dim3(1), dim3(DG_BLOCK), 0, s, block_sums, H3 / DG_BLOCK, cascade, w.n_occ);
+    hipLaunchKernelGGL(k_dg_occ_write, dim3(nblocks), dim3(DG_BLOCK), 0, s, density_grid, n, H3, block_sums, w.occ);
     hipLaunchKernelGGL(k_dg_sample_partial, dim3(ngp_div_up(cascade * N, DG_BLOCK)), dim3(DG_BLOCK), 0, s, cascade, N, H3, H, cc, seed, iteration,
                        w.occ, w.n_occ, xyzs, cells);
     NGP_CHECK_LAUNCH("density_grid_sample");
@@ -336,10 +323,10 @@ extern "C" int ngp_density_grid_update(const float* sigmas, const int32_t* cells
                                        float* mean_density, void* workspace, size_t workspace_bytes, void* stream) {
     NGP_REQUIRE(dg_shape_ok(cascade, H), "density_grid_update: cascade must be 1..8 and H a power of two in [8, 1024]");
     NGP_REQUIRE(sigmas && density_grid && bitfield && mean_density, "density_grid_update: null pointer");
-    NGP_REQUIRE(workspace && workspace_bytes >= ngp_density_grid_workspace(cascade, H), "density_grid_update: workspace too small");
+    const dg_ws w = dg_layout(cascade, H, workspace);
+    NGP_REQUIRE(workspace && workspace_bytes >= w.total, "density_grid_update: workspace too small");
     hipStream_t s = (hipStream_t)stream;
     const uint32_t n = cascade * H * H * H;
-    const dg_ws w = dg_carve(workspace, cascade, H);
     const uint32_t nb4 = ngp_div_up(n / 4, DG_BLOCK);
     if (cells) {
         hipLaunchKernelGGL(k_dg_fill, dim3(nb4), dim3(DG_BLOCK), 0, s, w.tmp, n / 4);

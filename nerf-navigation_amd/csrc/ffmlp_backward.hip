@@ -200,8 +200,7 @@ __global__ __launch_bounds__(256) void k_ffmlp_bwd_wgrad(wgrad_jobs jobs, uint32
 static uint32_t ffmlp_nparams(uint32_t in, uint32_t out, uint32_t hid, uint32_t nl) { return hid * (in + hid * (nl - 1) + out); }
 
 extern "C" size_t ngp_ffmlp_backward_workspace(uint32_t input_dim, uint32_t output_dim, uint32_t hidden_dim, uint32_t num_layers) {
-    // (the layer-by-layer path also keeps transposed copies of the weights there)
-    return ffmlp_generic_backward_workspace(input_dim, output_dim, hidden_dim, num_layers);
+    return ffmlp_backward_layout(input_dim, output_dim, hidden_dim, num_layers, nullptr).total;
 }
 
 template <int NHID, int INT>
@@ -235,7 +234,8 @@ extern "C" int ngp_ffmlp_backward(const void* grad, const void* inputs, const vo
     NGP_REQUIRE(activation == 0 && output_activation == 6, "ffmlp_backward: only ReLU hidden / no output activation");
     NGP_REQUIRE(B % 32 == 0, "ffmlp_backward: batch must be a multiple of 32 (the wrapper pads to 128)");
     const uint32_t nw = ffmlp_nparams(input_dim, output_dim, hidden_dim, num_layers);
-    NGP_REQUIRE(grad_weights && workspace && workspace_bytes >= ffmlp_partial_bytes(nw), "ffmlp_backward: grad_weights / workspace missing or too small");
+    const ffmlp_bwd_ws lay = ffmlp_backward_layout(input_dim, output_dim, hidden_dim, num_layers, workspace);
+    NGP_REQUIRE(grad_weights && workspace && workspace_bytes >= lay.partials_total, "ffmlp_backward: grad_weights / workspace missing or too small");
     hipStream_t s = (hipStream_t)stream;
     uint32_t gx = 0;                                                    // rows of partial sums written (0: an empty batch, all-zero gradients)
     if (B > 0) {
@@ -252,7 +252,7 @@ extern "C" int ngp_ffmlp_backward(const void* grad, const void* inputs, const vo
         // weight-gradient jobs (reference: ffmlp.cu:804-810, 851-857, 869-875)
         const _Float16* fb = (const _Float16*)forward_buffer;
         const _Float16* bb = (const _Float16*)backward_buffer;
-        float* ws = (float*)workspace;
+        float* ws = lay.partials;
         const uint64_t BW = (uint64_t)B * 64;
         const uint32_t off_hid = 64 * input_dim, off_last = off_hid + (num_layers - 1) * 64 * 64;
         wgrad_jobs jobs;
@@ -272,7 +272,7 @@ extern "C" int ngp_ffmlp_backward(const void* grad, const void* inputs, const vo
         // accumulate in half in an order its streams decide, ffmlp.cu:804-875; float atomics here made two identical runs differ in the last bits)
         hipLaunchKernelGGL(k_ffmlp_bwd_wgrad, dim3(gx, jobs.n), dim3(256), 0, s, jobs, B);
     }
-    ffmlp_sum_partials((const float*)workspace, gx, nw, grad_weights, s);
+    ffmlp_sum_partials(lay.partials, gx, nw, grad_weights, s);
     NGP_CHECK_LAUNCH("ffmlp_backward");
     return NGP_OK;
 }

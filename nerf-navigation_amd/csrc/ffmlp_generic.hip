@@ -167,7 +167,6 @@ uint32_t ffmlp_partial_rows(uint32_t nw) {
     const uint64_t fit = (64ull << 20) / (4ull * (nw ? nw : 1u));
     return (uint32_t)(fit > 256 ? 256 : (fit ? fit : 1));
 }
-size_t ffmlp_partial_bytes(uint32_t nw) { return ((size_t)ffmlp_partial_rows(nw) * nw * sizeof(float) + 255) & ~(size_t)255; }
 void ffmlp_sum_partials(const float* partials, uint32_t rows, uint32_t nw, void* grad_weights_half, hipStream_t s) {
     hipLaunchKernelGGL(k_fg_sum_partials, dim3(ngp_div_up(nw, FG_SUM_COLS)), dim3(FG_SUM_COLS * FG_SUM_CHUNKS), 0, s, partials, rows, nw, (_Float16*)grad_weights_half);
 }
@@ -216,9 +215,10 @@ int ffmlp_generic_forward(const void* inputs, const void* weights, uint32_t B, u
 
 static uint32_t fg_nparams(uint32_t in, uint32_t out, uint32_t hid, uint32_t nl) { return hid * (in + hid * (nl - 1) + out); }
 
-size_t ffmlp_generic_backward_workspace(uint32_t input_dim, uint32_t output_dim, uint32_t hidden_dim, uint32_t num_layers) {
+ffmlp_bwd_ws ffmlp_backward_layout(uint32_t input_dim, uint32_t output_dim, uint32_t hidden_dim, uint32_t num_layers, void* base) {
     const uint32_t nw = fg_nparams(input_dim, output_dim, hidden_dim, num_layers);
-    return ffmlp_partial_bytes(nw) + sizeof(_Float16) * (size_t)nw + 256;       // [partial sums of the weight gradients | transposed weights]
+    ngp_carver c(base);
+    return {c.take<float>((size_t)ffmlp_partial_rows(nw) * nw), c.total(256), c.take<_Float16>(nw), (c.take<unsigned char>(256, 1), c.total())};
 }
 
 int ffmlp_generic_backward(const void* grad, const void* inputs, const void* weights, const void* forward_buffer, uint32_t B, uint32_t input_dim,
@@ -226,10 +226,10 @@ int ffmlp_generic_backward(const void* grad, const void* inputs, const void* wei
                            void* backward_buffer, void* grad_inputs, void* grad_weights, void* workspace, size_t workspace_bytes, hipStream_t s) {
     NGP_REQUIRE(activation != FG_SINE, "ffmlp_backward: the Sine activation has no backward (the reference keeps post-activations only, utils.h:552-556)");
     const uint32_t nw = fg_nparams(input_dim, output_dim, hidden_dim, num_layers);
-    NGP_REQUIRE(grad_weights && workspace && workspace_bytes >= ffmlp_generic_backward_workspace(input_dim, output_dim, hidden_dim, num_layers),
-                "ffmlp_backward: grad_weights / workspace missing or too small");
-    float* ws = (float*)workspace;
-    _Float16* wt = (_Float16*)((unsigned char*)workspace + ffmlp_partial_bytes(nw));
+    const ffmlp_bwd_ws lay = ffmlp_backward_layout(input_dim, output_dim, hidden_dim, num_layers, workspace);
+    NGP_REQUIRE(grad_weights && workspace && workspace_bytes >= lay.total, "ffmlp_backward: grad_weights / workspace missing or too small");
+    float* ws = lay.partials;
+    _Float16* wt = (_Float16*)lay.weights_t;
     uint32_t gx = 0;                                                        // rows of partial sums written (0: an empty batch, all-zero gradients)
     if (B > 0) {
         NGP_REQUIRE(grad && inputs && weights && forward_buffer && backward_buffer, "ffmlp_backward: null pointer");

@@ -1,5 +1,4 @@
 // field_train.hip -- the training step of the field in native launches (forward keeps 64 B per sample; backward recomputes both networks).
-#include <atomic>
 #include "ngp_field.h"
 
 // ===========================================================================
@@ -690,7 +689,9 @@ __global__ __launch_bounds__(FT_FIN_COLS * FT_FIN_CHUNKS) void k_field_train_wgr
     }
 }
 
-extern "C" size_t ngp_field_train_saved_bytes(uint32_t M) { return (size_t)((M + 31) >> 5) * 2 * 64 * sizeof(ngp_h8); }
+// kept by the forward for the backward: the encoded features, one ngp_h8 per lane per 16-sample tile (64 B per sample)
+static ngp_array_ws<ngp_h8> ft_saved_layout(uint32_t M, void* base) { return ngp_array_layout<ngp_h8>((size_t)((M + 31) >> 5) * 2 * 64, base); }
+extern "C" size_t ngp_field_train_saved_bytes(uint32_t M) { return ft_saved_layout(M, nullptr).total; }
 // workgroups of the backward launches for M samples (persistent: at most one per CU), = rows of the partial-sum buffer
 static uint32_t ft_bwd_blocks(uint32_t M) {
     const uint32_t blocks = ngp_div_up((M + 31) >> 5, RF_BLOCK / 64);
@@ -751,21 +752,19 @@ __global__ __launch_bounds__(FT_LIVE_CHUNK) void k_ft_live_write(const uint32_t*
 
 // workspace: [per-workgroup f32 weight-gradient partial sums, ft_bwd_blocks(M) x 18,432 | the density-net output gradients of the live samples |
 //             live count (256 B) | per-chunk counts | bitmap | list of live samples]; nothing to clear
-static size_t ft_ws_outs_offset(uint32_t M) { return ((size_t)ft_bwd_blocks(M) * FT_WS_FLOATS * sizeof(float) + 255) & ~(size_t)255; }
-static size_t ft_ws_live_offset(uint32_t M) { return ft_ws_outs_offset(M) + (size_t)((M + 31) >> 5) * 2 * 64 * sizeof(ngp_h4); }
-static size_t ft_live_counts_bytes(size_t nch) { return (nch * 4 + 255) & ~(size_t)255; }
-static size_t ft_ws_live_bytes(uint32_t M) {
+struct ft_ws { float* wgrad; ngp_h4* grad_outs; uint32_t* live_count; uint32_t* live_counts; unsigned long long* live_bitmap; uint32_t* live_list; size_t total; };
+static ft_ws ft_layout(uint32_t M, void* base) {
     const size_t nch = ngp_div_up(M ? M : 1u, FT_LIVE_CHUNK);
-    return 256 + ft_live_counts_bytes(nch) + nch * (FT_LIVE_CHUNK / 64) * 8 + (((size_t)M + 31) & ~(size_t)31) * 4;
+    ngp_carver c(base);
+    return {c.take<float>((size_t)ft_bwd_blocks(M) * FT_WS_FLOATS, 1), c.take<ngp_h4>((size_t)((M + 31) >> 5) * 2 * 64), c.take<uint32_t>(64, 1), c.take<uint32_t>(nch, 1),
+            c.take<unsigned long long>(nch * (FT_LIVE_CHUNK / 64)), c.take<uint32_t>(((size_t)M + 31) & ~(size_t)31, 1), M ? c.total() : 0};   // an empty batch needs none
 }
-extern "C" size_t ngp_field_train_workspace(uint32_t M) { return M ? ft_ws_live_offset(M) + ft_ws_live_bytes(M) : 0; }
+extern "C" size_t ngp_field_train_workspace(uint32_t M) { return ft_layout(M, nullptr).total; }
 // where the last ngp_field_train_backward(.., workspace, .., M) left its list of live samples and their number (device pointers into that workspace)
 extern "C" int ngp_field_train_live_list(void* workspace, uint32_t M, const uint32_t** list, const uint32_t** count) {
     NGP_REQUIRE(workspace && list && count && M > 0, "field_train_live_list: null pointer or empty batch");
-    unsigned char* base = static_cast<unsigned char*>(workspace) + ft_ws_live_offset(M);
-    const size_t nch = ngp_div_up(M, FT_LIVE_CHUNK);
-    *count = reinterpret_cast<const uint32_t*>(base);
-    *list = reinterpret_cast<const uint32_t*>(base + 256 + ft_live_counts_bytes(nch) + nch * (FT_LIVE_CHUNK / 64) * 8);
+    const ft_ws w = ft_layout(M, workspace);
+    *count = w.live_count; *list = w.live_list;
     return NGP_OK;
 }
 
@@ -836,7 +835,9 @@ __global__ __launch_bounds__(RF_BLOCK, 4) void k_field_density_mlp(rf_params P, 
     }
 }
 
-extern "C" size_t ngp_field_density_workspace(uint32_t M) { return (size_t)RF_L * (((size_t)(M + 31) >> 5) << 5) * sizeof(uint32_t); }
+// workspace: the encoded features of the padded batch, level by level (k_ft_encode_levels' output)
+static ngp_array_ws<uint32_t> fd_layout(uint32_t M, void* base) { return ngp_array_layout<uint32_t>((size_t)RF_L * (((size_t)(M + 31) >> 5) << 5), base); }
+extern "C" size_t ngp_field_density_workspace(uint32_t M) { return fd_layout(M, nullptr).total; }
 
 extern "C" int ngp_field_density(const ngp_field_t* field_host, const float* xyzs, uint32_t M, float* sigmas, void* workspace, size_t workspace_bytes,
                                  void* stream) {
@@ -845,12 +846,13 @@ extern "C" int ngp_field_density(const ngp_field_t* field_host, const float* xyz
     if (rc != NGP_OK) return rc;
     if (M == 0) return NGP_OK;
     NGP_REQUIRE(xyzs && sigmas && workspace, "field_density: null pointer");
-    NGP_REQUIRE(workspace_bytes >= ngp_field_density_workspace(M), "field_density: workspace too small (ngp_field_density_workspace)");
+    const auto w = fd_layout(M, workspace);
+    NGP_REQUIRE(workspace_bytes >= w.total, "field_density: workspace too small (ngp_field_density_workspace)");
     const uint32_t npairs = (M + 31) >> 5, Mp = npairs << 5;
-    hipLaunchKernelGGL(k_ft_encode_levels, dim3(ngp_div_up(Mp, 256u * FT_ENC_SPT), RF_L), dim3(256), 0, (hipStream_t)stream, P, xyzs, M, Mp, (uint32_t*)workspace);
+    hipLaunchKernelGGL(k_ft_encode_levels, dim3(ngp_div_up(Mp, 256u * FT_ENC_SPT), RF_L), dim3(256), 0, (hipStream_t)stream, P, xyzs, M, Mp, w.p);
     uint32_t blocks = ngp_div_up(npairs, RF_BLOCK / 64);
     if (blocks > 256 * 4) blocks = 256 * 4;
-    hipLaunchKernelGGL(k_field_density_mlp, dim3(blocks), dim3(RF_BLOCK), 14 * 1024, (hipStream_t)stream, P, (const uint32_t*)workspace, M, sigmas);
+    hipLaunchKernelGGL(k_field_density_mlp, dim3(blocks), dim3(RF_BLOCK), 14 * 1024, (hipStream_t)stream, P, (const uint32_t*)w.p, M, sigmas);
     NGP_CHECK_LAUNCH("field_density");
     return NGP_OK;
 }
@@ -868,22 +870,21 @@ extern "C" int ngp_field_train_forward(const ngp_field_t* field_host, const floa
     if (rc != NGP_OK) return rc;
     if (M == 0) return NGP_OK;
     NGP_REQUIRE(xyzs && dirs && sigmas && rgbs && saved, "field_train_forward: null pointer");
-    NGP_REQUIRE(saved_bytes >= ngp_field_train_saved_bytes(M), "field_train_forward: saved buffer too small (%zu < %zu bytes)", saved_bytes,
-                ngp_field_train_saved_bytes(M));
+    const auto kept = ft_saved_layout(M, saved);
+    NGP_REQUIRE(saved_bytes >= kept.total, "field_train_forward: saved buffer too small (%zu < %zu bytes)", saved_bytes, kept.total);
     const uint32_t npairs = (M + 31) >> 5, Mp = npairs << 5;
     uint32_t blocks = ngp_div_up(npairs, RF_BLOCK / 64);
     if (blocks > 256 * FT_FWD_WG_PER_CU) blocks = 256 * FT_FWD_WG_PER_CU;
     const bool two_pass = ft_two_pass.load(std::memory_order_relaxed) != 0 && M >= FT_TWO_PASS_MIN;
     if (two_pass) {
-        hipLaunchKernelGGL(k_ft_encode_levels, dim3(ngp_div_up(Mp, 256u * FT_ENC_SPT), RF_L), dim3(256), 0, (hipStream_t)stream, P, xyzs, M, Mp, (uint32_t*)saved);
+        hipLaunchKernelGGL(k_ft_encode_levels, dim3(ngp_div_up(Mp, 256u * FT_ENC_SPT), RF_L), dim3(256), 0, (hipStream_t)stream, P, xyzs, M, Mp, (uint32_t*)kept.p);
         NGP_CHECK_LAUNCH("field_train_forward (encode)");
     }
-    hipLaunchKernelGGL(k_field_train_forward, dim3(blocks), dim3(RF_BLOCK), 36 * 1024, (hipStream_t)stream, P, xyzs, dirs, M, sigmas, rgbs, (uint32_t*)saved, two_pass);
+    hipLaunchKernelGGL(k_field_train_forward, dim3(blocks), dim3(RF_BLOCK), 36 * 1024, (hipStream_t)stream, P, xyzs, dirs, M, sigmas, rgbs, (uint32_t*)kept.p, two_pass);
     NGP_CHECK_LAUNCH("field_train_forward");
     return NGP_OK;
 }
 
-static std::atomic<unsigned> ft_big_lds_set{0};
 // process-wide switch for A/B timing and tests: 0 = the backward treats every sample as live (the list is the identity)
 static std::atomic<int> ft_live_only{1};
 extern "C" int ngp_field_train_set_live_only(int enabled) { return ft_live_only.exchange(enabled ? 1 : 0, std::memory_order_relaxed); }
@@ -896,38 +897,30 @@ extern "C" int ngp_field_train_backward(const ngp_field_t* field_host, const voi
     int rc = rf_fill_params("field_train_backward", field_host, P);
     if (rc != NGP_OK) return rc;
     NGP_REQUIRE(grad_sigma_weights && grad_color_weights && workspace, "field_train_backward: null pointer");
-    NGP_REQUIRE(workspace_bytes >= ngp_field_train_workspace(M), "field_train_backward: workspace too small");
+    const ft_ws w = ft_layout(M, workspace);
+    NGP_REQUIRE(workspace_bytes >= w.total, "field_train_backward: workspace too small");
     if (M > 0) {
         NGP_REQUIRE(saved && dirs && grad_sigmas && grad_rgbs && grad_enc, "field_train_backward: null pointer");
-        int dev = 0;
-        NGP_REQUIRE(hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 32, "field_train_backward: no current device");
-        if (!(ft_big_lds_set.load(std::memory_order_acquire) & (1u << dev))) {
-            NGP_REQUIRE(hipFuncSetAttribute(reinterpret_cast<const void*>(k_field_train_backward<0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FT_LDS) == hipSuccess &&
-                        hipFuncSetAttribute(reinterpret_cast<const void*>(k_field_train_backward<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FT_LDS) == hipSuccess,
-                        "field_train_backward: cannot reserve %u bytes of LDS", FT_LDS);
-            ft_big_lds_set.fetch_or(1u << dev, std::memory_order_release);
-        }
+        static std::atomic<unsigned long long> lds_devices{0};
+        const int rc_lds = ngp_allow_dynamic_lds(lds_devices, {reinterpret_cast<const void*>(k_field_train_backward<0>),
+                                                               reinterpret_cast<const void*>(k_field_train_backward<1>)}, FT_LDS);
+        NGP_REQUIRE(rc_lds != NGP_LDS_NO_DEVICE, "field_train_backward: no current device");
+        NGP_REQUIRE(rc_lds == NGP_LDS_OK, "field_train_backward: cannot reserve %u bytes of LDS", FT_LDS);
         const uint32_t blocks = ft_bwd_blocks(M);
-        unsigned char* ws = static_cast<unsigned char*>(workspace);
-        ngp_h4* grad_outs = reinterpret_cast<ngp_h4*>(ws + ft_ws_outs_offset(M));
         const uint32_t nch = ngp_div_up(M, FT_LIVE_CHUNK);
-        uint32_t* live_count = reinterpret_cast<uint32_t*>(ws + ft_ws_live_offset(M));
-        uint32_t* live_counts = live_count + 64;
-        unsigned long long* live_bitmap = reinterpret_cast<unsigned long long*>(reinterpret_cast<unsigned char*>(live_counts) + ft_live_counts_bytes(nch));
-        uint32_t* live_list = reinterpret_cast<uint32_t*>(live_bitmap + (size_t)nch * (FT_LIVE_CHUNK / 64));
-        hipLaunchKernelGGL(k_ft_live_count, dim3(nch), dim3(FT_LIVE_CHUNK), 0, (hipStream_t)stream, grad_sigmas, grad_rgbs, M, live_counts, live_bitmap,
+        hipLaunchKernelGGL(k_ft_live_count, dim3(nch), dim3(FT_LIVE_CHUNK), 0, (hipStream_t)stream, grad_sigmas, grad_rgbs, M, w.live_counts, w.live_bitmap,
                            (live_only && ft_live_only.load(std::memory_order_relaxed)) ? 0u : 1u);
-        hipLaunchKernelGGL(k_ft_live_write, dim3(nch), dim3(FT_LIVE_CHUNK), 0, (hipStream_t)stream, live_counts, live_bitmap, nch, live_list, live_count);
+        hipLaunchKernelGGL(k_ft_live_write, dim3(nch), dim3(FT_LIVE_CHUNK), 0, (hipStream_t)stream, w.live_counts, w.live_bitmap, nch, w.live_list, w.live_count);
         NGP_CHECK_LAUNCH("field_train_backward (live samples)");
         hipLaunchKernelGGL(k_field_train_backward<0>, dim3(blocks), dim3(RF_BLOCK), FT_LDS, (hipStream_t)stream, P, (const uint32_t*)saved, dirs, M,
-                           grad_sigmas, grad_rgbs, grad_outs, (_Float16*)grad_enc, (float*)workspace, live_count, live_list);
+                           grad_sigmas, grad_rgbs, w.grad_outs, (_Float16*)grad_enc, w.wgrad, w.live_count, w.live_list);
         NGP_CHECK_LAUNCH("field_train_backward (colour net)");
         hipLaunchKernelGGL(k_field_train_backward<1>, dim3(blocks), dim3(RF_BLOCK), FT_LDS, (hipStream_t)stream, P, (const uint32_t*)saved, dirs, M,
-                           grad_sigmas, grad_rgbs, grad_outs, (_Float16*)grad_enc, (float*)workspace, live_count, live_list);
+                           grad_sigmas, grad_rgbs, w.grad_outs, (_Float16*)grad_enc, w.wgrad, w.live_count, w.live_list);
         NGP_CHECK_LAUNCH("field_train_backward (density net)");
     }
     static_assert(FT_WS_FLOATS % FT_FIN_COLS == 0, "finish: whole column groups");
-    hipLaunchKernelGGL(k_field_train_wgrad_finish, dim3(FT_WS_FLOATS / FT_FIN_COLS), dim3(FT_FIN_COLS * FT_FIN_CHUNKS), 0, (hipStream_t)stream, (const float*)workspace,
+    hipLaunchKernelGGL(k_field_train_wgrad_finish, dim3(FT_WS_FLOATS / FT_FIN_COLS), dim3(FT_FIN_COLS * FT_FIN_CHUNKS), 0, (hipStream_t)stream, (const float*)w.wgrad,
                        M > 0 ? ft_bwd_blocks(M) : 0u, grad_sigma_weights, grad_color_weights);
     NGP_CHECK_LAUNCH("field_train_wgrad_finish");
     return NGP_OK;

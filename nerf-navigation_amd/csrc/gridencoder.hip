@@ -9,7 +9,6 @@
 // Arithmetic is the reference's, operation for operation: positions and weights in binary32, accumulation in the
 // table dtype (c10::Half arithmetic = compute in float, round to half after every operation).
 #include "ngp_device.h"
-#include <atomic>
 
 static constexpr uint32_t GE_MAX_LEVELS = 32;
 
@@ -20,8 +19,8 @@ struct ge_levels {
 
 static void ge_fill_levels(ge_levels& lv, uint32_t L, float S, uint32_t H) {
     for (uint32_t l = 0; l < L; l++) {
-        lv.scale[l] = exp2f((float)l * S) * (float)H - 1.0f;
-        lv.resolution[l] = (uint32_t)ceilf(lv.scale[l]) + 1u;
+        lv.scale[l] = ngp_level_scale(l, S, H);
+        lv.resolution[l] = ngp_level_resolution(lv.scale[l]);
     }
 }
 
@@ -731,22 +730,21 @@ __device__ __forceinline__ bool gs_half_to_fixed(uint32_t bits, long long& q) {
     return e != 31u;
 }
 
-struct gs_ws {                                         // workspace layout (byte offsets), computed on the host
-    size_t vals, rows, dir, ticket, total;
+struct gs_ws {                                         // workspace layout, computed on the host
+    uint32_t* ticket;                                  // [1] u32 (+ padding to 256 B)
+    uint16_t* dir;                                     // [L][GS_MAX_SLICES + 1][nchunks] u16
+    uint32_t* vals;                                    // [L][nchunks][GS_REGION] u32, 256-byte aligned
+    uint16_t* rows;                                    // [L][nchunks][GS_REGION] u16
+    size_t total;
     uint32_t nchunks;
 };
 
-static gs_ws gs_layout(uint32_t B, uint32_t L) {
-    gs_ws w;
-    const uint32_t b = B < GS_PASS_SAMPLES ? B : GS_PASS_SAMPLES;
-    w.nchunks = ngp_div_up(b, GS_CHUNK);
-    const size_t regions = (size_t)L * w.nchunks;
-    w.ticket = 0;                                      // [1] u32 (+ padding to 256 B)
-    w.dir = 256;                                       // [L][GS_MAX_SLICES + 1][nchunks] u16
-    w.vals = w.dir + (((size_t)L * (GS_MAX_SLICES + 1) * w.nchunks * 2 + 255) & ~(size_t)255);   // [L][nchunks][GS_REGION] u32
-    w.rows = w.vals + regions * GS_REGION * 4;                                                // [L][nchunks][GS_REGION] u16
-    w.total = w.rows + regions * GS_REGION * 2;
-    return w;
+static gs_ws gs_layout(uint32_t B, uint32_t L, void* base) {
+    const uint32_t nchunks = ngp_div_up(B < GS_PASS_SAMPLES ? B : GS_PASS_SAMPLES, GS_CHUNK);
+    const size_t regions = (size_t)L * nchunks;
+    ngp_carver c(base);
+    return {c.take<uint32_t>(64, 1), c.take<uint16_t>((size_t)L * (GS_MAX_SLICES + 1) * nchunks, 1), c.take<uint32_t>(regions * GS_REGION),
+            c.take<uint16_t>(regions * GS_REGION, 1), c.total(), nchunks};
 }
 
 __global__ __launch_bounds__(1024) void k_gs_bin(const _Float16* __restrict__ grad, const float* __restrict__ inputs, const int* __restrict__ offsets,
@@ -991,7 +989,7 @@ __global__ __launch_bounds__(1024) void k_gs_accumulate(const uint32_t* __restri
 }
 
 extern "C" size_t ngp_grid_scatter_binned_workspace(uint32_t B, uint32_t L) {
-    return gs_layout(B, L).total;
+    return gs_layout(B, L, nullptr).total;
 }
 
 static int gs_run(const char* who, const void* grad, const float* inputs, const int32_t* offsets, void* grad_embeddings, uint32_t B, uint32_t L, float S, uint32_t H,
@@ -1007,25 +1005,17 @@ static int gs_run(const char* who, const void* grad, const float* inputs, const 
                 "%s: a level may have at most 2^19 rows (use grid_encode_backward for larger tables)", who);
     const bool split = !(do_bin && do_sum && level_lo == 0 && level_hi == L);
     NGP_REQUIRE(!split || B <= GS_PASS_SAMPLES, "%s: binning and summing in separate calls needs B <= 2^22 samples (one pass)", who);
-    const gs_ws w = gs_layout(B, L);
+    const gs_ws w = gs_layout(B, L, workspace);
     NGP_REQUIRE(workspace && workspace_bytes >= w.total, "%s: workspace too small (see ngp_grid_scatter_binned_workspace)", who);
     hipStream_t s = (hipStream_t)stream;
     ge_levels lv;
     ge_fill_levels(lv, L, S, H);
-    char* base = (char*)workspace;
     const size_t lds = (size_t)GS_SLICE_ROWS * 2 * sizeof(unsigned long long);
     int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0) return ngp_fail(NGP_ELAUNCH, "%s: no current device", who);
-    {   // the raised dynamic-LDS limit is a per-DEVICE function attribute: set once on every device this process scatters on (one process may drive several)
-        static std::atomic<unsigned long long> lds_devices{0};
-        const unsigned long long bit = 1ull << (dev & 63);
-        if (dev >= 64 || !(lds_devices.load(std::memory_order_acquire) & bit)) {
-            if (hipFuncSetAttribute((const void*)k_gs_accumulate<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
-                hipFuncSetAttribute((const void*)k_gs_accumulate<_Float16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-                return ngp_fail(NGP_ELAUNCH, "%s: cannot reserve %zu bytes of LDS", who, lds);
-            lds_devices.fetch_or(bit, std::memory_order_release);
-        }
-    }
+    static std::atomic<unsigned long long> lds_devices{0};
+    const int rc_lds = ngp_allow_dynamic_lds(lds_devices, {(const void*)k_gs_accumulate<float>, (const void*)k_gs_accumulate<_Float16>}, lds, &dev);
+    if (rc_lds == NGP_LDS_NO_DEVICE) return ngp_fail(NGP_ELAUNCH, "%s: no current device", who);
+    if (rc_lds != NGP_LDS_OK) return ngp_fail(NGP_ELAUNCH, "%s: cannot reserve %zu bytes of LDS", who, lds);
     int cus = 256;
     {   // (hipGetDeviceProperties fills a 1.5 KB structure through the driver on every call: asked once per device)
         static std::atomic<int> cu_count[64];
@@ -1045,19 +1035,19 @@ static int gs_run(const char* who, const void* grad, const float* inputs, const 
         const uint32_t count = B - first < GS_PASS_SAMPLES ? B - first : GS_PASS_SAMPLES;
         const uint32_t nchunks = count ? ngp_div_up(count, GS_CHUNK) : 0u;
         if (do_bin && nchunks)
-            hipLaunchKernelGGL(k_gs_bin, dim3(nchunks, L), dim3(GS_CHUNK), 0, s, (const _Float16*)grad, inputs, offsets, (uint32_t*)(base + w.vals),
-                               (uint16_t*)(base + w.rows), (uint16_t*)(base + w.dir), B, first, count, nchunks, lv, gridtype, align_corners != 0,
-                               do_sum ? (uint32_t*)(base + w.ticket) : (uint32_t*)nullptr, list, list_count);
+            hipLaunchKernelGGL(k_gs_bin, dim3(nchunks, L), dim3(GS_CHUNK), 0, s, (const _Float16*)grad, inputs, offsets, w.vals,
+                               w.rows, w.dir, B, first, count, nchunks, lv, gridtype, align_corners != 0,
+                               do_sum ? w.ticket : (uint32_t*)nullptr, list, list_count);
         if (do_sum) {
             // the ticket starts at zero: the bin launch just before wrote it, otherwise (no bin launch in this call) a memset does
-            if (!(do_bin && nchunks) && hipMemsetAsync(base + w.ticket, 0, 4, s) != hipSuccess) return ngp_fail(NGP_ELAUNCH, "%s: memset failed", who);
+            if (!(do_bin && nchunks) && hipMemsetAsync(w.ticket, 0, 4, s) != hipSuccess) return ngp_fail(NGP_ELAUNCH, "%s: memset failed", who);
             if (out_dtype == NGP_F32)
-                hipLaunchKernelGGL(k_gs_accumulate<float>, dim3(cus), dim3(1024), lds, s, (const uint32_t*)(base + w.vals), (const uint16_t*)(base + w.rows),
-                                   (const uint16_t*)(base + w.dir), offsets, (uint32_t*)(base + w.ticket), (float*)grad_embeddings, level_lo, level_hi, nchunks,
+                hipLaunchKernelGGL(k_gs_accumulate<float>, dim3(cus), dim3(1024), lds, s, (const uint32_t*)w.vals, (const uint16_t*)w.rows,
+                                   (const uint16_t*)w.dir, offsets, w.ticket, (float*)grad_embeddings, level_lo, level_hi, nchunks,
                                    out_scale, add);
             else
-                hipLaunchKernelGGL(k_gs_accumulate<_Float16>, dim3(cus), dim3(1024), lds, s, (const uint32_t*)(base + w.vals), (const uint16_t*)(base + w.rows),
-                                   (const uint16_t*)(base + w.dir), offsets, (uint32_t*)(base + w.ticket), (_Float16*)grad_embeddings, level_lo, level_hi, nchunks,
+                hipLaunchKernelGGL(k_gs_accumulate<_Float16>, dim3(cus), dim3(1024), lds, s, (const uint32_t*)w.vals, (const uint16_t*)w.rows,
+                                   (const uint16_t*)w.dir, offsets, w.ticket, (_Float16*)grad_embeddings, level_lo, level_hi, nchunks,
                                    out_scale, add);
         }
         first += count;

@@ -20,7 +20,6 @@
 //
 // Arithmetic: float32 like the reference path, but sums are fused multiply-adds in a fixed order of their own (rocBLAS has its own):
 // results agree with the torch path to float32 rounding (tests/test_gpu_nav_native.py states the tolerances against the CPU oracle).
-#include <atomic>
 #include "ngp_sh.h"
 
 #ifndef NV_RUN_U
@@ -713,22 +712,25 @@ __global__ __launch_bounds__(256) void k_nav_transpose(const float* __restrict__
     dst[c * rows + r] = src[t];
 }
 
-static constexpr size_t NV_PREP_W1T = 0, NV_PREP_W2T = 32 * 64, NV_PREP_V0T = NV_PREP_W2T + 64 * 16, NV_PREP_V1T = NV_PREP_V0T + 31 * 64,
-                        NV_PREP_V2T = NV_PREP_V1T + 64 * 64, NV_PREP_FLOATS = NV_PREP_V2T + 64 * 3;
-
-extern "C" size_t ngp_nav_field_workspace(void) { return sizeof(float) * NV_PREP_FLOATS; }
+// the prepared workspace: transposed copies of the five weight matrices, back to back
+struct nav_prep_ws { float* w1t; float* w2t; float* v0t; float* v1t; float* v2t; size_t total; };
+static nav_prep_ws nav_prep_layout(void* base) {
+    ngp_carver c(base);
+    return {c.take<float>(32 * 64, 1), c.take<float>(64 * 16, 1), c.take<float>(31 * 64, 1), c.take<float>(64 * 64, 1), c.take<float>(64 * 3, 1), c.total()};
+}
+extern "C" size_t ngp_nav_field_workspace(void) { return nav_prep_layout(nullptr).total; }
 
 // transposed copies of the five weight matrices into `workspace`; call again whenever the weights change
 extern "C" int ngp_nav_field_prepare(const ngp_nav_field_t* f, void* workspace, size_t workspace_bytes, void* stream) {
     NGP_REQUIRE(f && f->sigma_w0 && f->color_w1 && workspace && workspace_bytes >= ngp_nav_field_workspace(), "nav_field_prepare: bad argument");
     NGP_REQUIRE(f->sigma_w1 && f->color_w0 && f->color_w2, "nav_field_prepare: null weight pointer");
-    float* w = (float*)workspace;
+    const nav_prep_ws w = nav_prep_layout(workspace);
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_nav_transpose, dim3(8), dim3(256), 0, st, f->sigma_w0, 64u, 32u, w + NV_PREP_W1T);
-    hipLaunchKernelGGL(k_nav_transpose, dim3(4), dim3(256), 0, st, f->sigma_w1, 16u, 64u, w + NV_PREP_W2T);
-    hipLaunchKernelGGL(k_nav_transpose, dim3(8), dim3(256), 0, st, f->color_w0, 64u, 31u, w + NV_PREP_V0T);
-    hipLaunchKernelGGL(k_nav_transpose, dim3(16), dim3(256), 0, st, f->color_w1, 64u, 64u, w + NV_PREP_V1T);
-    hipLaunchKernelGGL(k_nav_transpose, dim3(1), dim3(256), 0, st, f->color_w2, 3u, 64u, w + NV_PREP_V2T);
+    hipLaunchKernelGGL(k_nav_transpose, dim3(8), dim3(256), 0, st, f->sigma_w0, 64u, 32u, w.w1t);
+    hipLaunchKernelGGL(k_nav_transpose, dim3(4), dim3(256), 0, st, f->sigma_w1, 16u, 64u, w.w2t);
+    hipLaunchKernelGGL(k_nav_transpose, dim3(8), dim3(256), 0, st, f->color_w0, 64u, 31u, w.v0t);
+    hipLaunchKernelGGL(k_nav_transpose, dim3(16), dim3(256), 0, st, f->color_w1, 64u, 64u, w.v1t);
+    hipLaunchKernelGGL(k_nav_transpose, dim3(1), dim3(256), 0, st, f->color_w2, 3u, 64u, w.v2t);
     NGP_CHECK_LAUNCH("nav_field_prepare");
     return NGP_OK;
 }
@@ -736,16 +738,10 @@ extern "C" int ngp_nav_field_prepare(const ngp_nav_field_t* f, void* workspace, 
 // the kernels use slightly more than the default 64 KiB of dynamic LDS; the raised limit is a per-device function attribute
 static int nav_allow_big_lds() {
     static std::atomic<unsigned long long> devices{0};
-    int device = 0;
-    if (hipGetDevice(&device) != hipSuccess || device < 0) return ngp_fail(NGP_ELAUNCH, "nav: no current device");
-    const unsigned long long bit = 1ull << (device & 63);
-    if (device < 64 && (devices.load(std::memory_order_acquire) & bit)) return NGP_OK;
-    const void* kernels[5] = {(const void*)k_nav_density_fwd, (const void*)k_nav_density_bwd, (const void*)k_nav_run_fwd, (const void*)k_nav_run_bwd,
-                              (const void*)k_nav_density_vj};
-    for (const void* k : kernels)
-        if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-            return ngp_fail(NGP_ELAUNCH, "nav: cannot raise the dynamic LDS limit");
-    devices.fetch_or(bit, std::memory_order_release);
+    const int rc = ngp_allow_dynamic_lds(devices, {(const void*)k_nav_density_fwd, (const void*)k_nav_density_bwd, (const void*)k_nav_run_fwd,
+                                                   (const void*)k_nav_run_bwd, (const void*)k_nav_density_vj}, 160 * 1024);
+    if (rc == NGP_LDS_NO_DEVICE) return ngp_fail(NGP_ELAUNCH, "nav: no current device");
+    if (rc != NGP_LDS_OK) return ngp_fail(NGP_ELAUNCH, "nav: cannot raise the dynamic LDS limit");
     return NGP_OK;
 }
 
@@ -754,17 +750,14 @@ static int nav_fill(const char* who, const ngp_nav_field_t* f, const void* prepa
                 "%s: null field pointer", who);
     NGP_REQUIRE(f->L == NV_L && f->bound > 0.0f, "%s: the fused nav queries are built for the default field (16 levels x 2 features, 32-64-16 | 31-64-64-3)", who);
     P.table = (const float2*)f->embeddings;
-    const float* prep = (const float*)prepared;
-    P.w1t = (nv_wptr)(uintptr_t)(prep + NV_PREP_W1T);
-    P.w2t = (nv_wptr)(uintptr_t)(prep + NV_PREP_W2T);
-    P.v0t = (nv_wptr)(uintptr_t)(prep + NV_PREP_V0T);
-    P.v1t = (nv_wptr)(uintptr_t)(prep + NV_PREP_V1T);
-    P.v2t = (nv_wptr)(uintptr_t)(prep + NV_PREP_V2T);
+    const nav_prep_ws prep = nav_prep_layout(const_cast<void*>(prepared));
+    P.w1t = (nv_wptr)(uintptr_t)prep.w1t; P.w2t = (nv_wptr)(uintptr_t)prep.w2t;
+    P.v0t = (nv_wptr)(uintptr_t)prep.v0t; P.v1t = (nv_wptr)(uintptr_t)prep.v1t; P.v2t = (nv_wptr)(uintptr_t)prep.v2t;
     P.w2 = (nv_wptr)(uintptr_t)f->sigma_w1; P.v0 = (nv_wptr)(uintptr_t)f->color_w0;
     P.v1 = (nv_wptr)(uintptr_t)f->color_w1; P.v2 = (nv_wptr)(uintptr_t)f->color_w2;
     for (int l = 0; l < NV_L; l++) {
-        const float sc = exp2f((float)l * f->S) * (float)f->H - 1.0f;     // gridencoder.cu:126 on the host, as everywhere else
-        const uint32_t rs = (uint32_t)ceilf(sc) + 1u;
+        const float sc = ngp_level_scale((uint32_t)l, f->S, f->H);
+        const uint32_t rs = ngp_level_resolution(sc);
         const uint32_t o0 = (uint32_t)f->offsets_host[l], size = (uint32_t)f->offsets_host[l + 1] - o0;
         uint32_t stride = 1, s1 = 0, s2 = 0;
         bool dense = true;
@@ -827,7 +820,8 @@ extern "C" int ngp_nav_density_value_jac(const ngp_nav_field_t* f, const void* p
     return NGP_OK;
 }
 
-extern "C" size_t ngp_nav_run_saved_bytes(uint32_t N, uint32_t num_steps) { return sizeof(uint32_t) * NV_REC_WORDS * (size_t)N * num_steps; }
+static ngp_array_ws<uint32_t> nav_saved_layout(uint32_t N, uint32_t num_steps, void* base) { return ngp_array_layout<uint32_t>(NV_REC_WORDS * (size_t)N * num_steps, base); }
+extern "C" size_t ngp_nav_run_saved_bytes(uint32_t N, uint32_t num_steps) { return nav_saved_layout(N, num_steps, nullptr).total; }
 
 static int nav_run_args(const char* who, const float* rays_o, const float* rays_d, const float* nears, const float* fars, uint32_t N, uint32_t T,
                         const float* aabb_host, const float* bg_host, nav_run& R) {
@@ -850,10 +844,11 @@ extern "C" int ngp_nav_run_forward(const ngp_nav_field_t* f, const void* prepare
     rc = nav_run_args("nav_run_forward", rays_o, rays_d, nears, fars, N, num_steps, aabb_host, bg_color3_host, R);
     if (rc != NGP_OK) return rc;
     NGP_REQUIRE(image && depth && weights_sum, "nav_run_forward: null output");
-    NGP_REQUIRE(!saved || saved_bytes >= ngp_nav_run_saved_bytes(N, num_steps), "nav_run_forward: `saved` is smaller than ngp_nav_run_saved_bytes(N, num_steps)");
+    const auto kept = nav_saved_layout(N, num_steps, saved);
+    NGP_REQUIRE(!saved || saved_bytes >= kept.total, "nav_run_forward: `saved` is smaller than ngp_nav_run_saved_bytes(N, num_steps)");
     const size_t lds = sizeof(float) * (16 + NV_H * NV_BLOCK);
     { const int rc_lds = nav_allow_big_lds(); if (rc_lds != NGP_OK) return rc_lds; }
-    hipLaunchKernelGGL(k_nav_run_fwd, dim3(N), dim3(NV_BLOCK), lds, (hipStream_t)stream, P, R, image, depth, weights_sum, (uint32_t*)saved);
+    hipLaunchKernelGGL(k_nav_run_fwd, dim3(N), dim3(NV_BLOCK), lds, (hipStream_t)stream, P, R, image, depth, weights_sum, kept.p);
     NGP_CHECK_LAUNCH("nav_run_forward");
     return NGP_OK;
 }
@@ -870,11 +865,12 @@ extern "C" int ngp_nav_run_backward(const ngp_nav_field_t* f, const void* prepar
     rc = nav_run_args("nav_run_backward", rays_o, rays_d, nears, fars, N, num_steps, aabb_host, bg_color3_host, R);
     if (rc != NGP_OK) return rc;
     NGP_REQUIRE(grad_image && grad_rays_o && grad_rays_d, "nav_run_backward: null pointer");
-    NGP_REQUIRE(saved && saved_bytes >= ngp_nav_run_saved_bytes(N, num_steps), "nav_run_backward: needs the `saved` buffer its forward filled");
+    const auto kept = nav_saved_layout(N, num_steps, const_cast<void*>(saved));
+    NGP_REQUIRE(saved && saved_bytes >= kept.total, "nav_run_backward: needs the `saved` buffer its forward filled");
     const size_t lds = sizeof(float) * (16 + NV_H * NV_BLOCK);
     { const int rc_lds = nav_allow_big_lds(); if (rc_lds != NGP_OK) return rc_lds; }
     hipLaunchKernelGGL(k_nav_run_bwd, dim3(N), dim3(NV_BLOCK), lds, (hipStream_t)stream, P, R, grad_image, grad_depth, grad_weights_sum,
-                       (const uint32_t*)saved, grad_rays_o, grad_rays_d);
+                       (const uint32_t*)kept.p, grad_rays_o, grad_rays_d);
     NGP_CHECK_LAUNCH("nav_run_backward");
     return NGP_OK;
 }

@@ -17,8 +17,6 @@
 // No atomics; every sum runs in a fixed order, so two runs are bit-identical.
 #include "ngp_device.h"
 
-#include <atomic>
-#include <math.h>
 
 #define NP_HD __host__ __device__ __forceinline__
 
@@ -519,13 +517,15 @@ __global__ __launch_bounds__(NP_K3_THREADS) void k_plan_cost_step(np_args Aarg, 
 // host
 // ---------------------------------------------------------------------------
 
-static size_t np_align(size_t n) { return (n + 255) & ~(size_t)255; }
-
-extern "C" size_t ngp_plan_workspace(uint32_t R, uint32_t B) {
-    if (R < NP_MIN_R || R > NP_MAX_R || B < 1 || B > NP_MAX_B) return 0;
+// workspace (256-byte aligned pieces): body points of every state [(R + 3) B][3] | their density | its Jacobian [..][3]
+struct np_ws { float* points; float* sigma; float* jac; size_t total; };
+static np_ws np_layout(uint32_t R, uint32_t B, void* base) {
+    if (R < NP_MIN_R || R > NP_MAX_R || B < 1 || B > NP_MAX_B) return {};          // total 0: a shape no planner call accepts
     const size_t n = (size_t)(R + 3) * B;
-    return np_align(sizeof(float) * 3 * n) + np_align(sizeof(float) * n) + np_align(sizeof(float) * 3 * n);
+    ngp_carver c(base);
+    return {c.take<float>(3 * n), c.take<float>(n), c.take<float>(3 * n), c.total(256)};
 }
+extern "C" size_t ngp_plan_workspace(uint32_t R, uint32_t B) { return np_layout(R, B, nullptr).total; }
 
 static int np_fill(const char* who, const ngp_plan_cfg_t* c, uint32_t R, uint32_t B, np_args& A) {
     NGP_REQUIRE(c, "%s: null cfg", who);
@@ -552,15 +552,9 @@ static int np_fill(const char* who, const ngp_plan_cfg_t* c, uint32_t R, uint32_
 // the kernels keep all S <= 258 rows in LDS (66 KB): above the default dynamic limit, raised once per device
 static int np_allow_lds() {
     static std::atomic<unsigned long long> devices{0};
-    int device = 0;
-    if (hipGetDevice(&device) != hipSuccess || device < 0) return ngp_fail(NGP_ELAUNCH, "plan: no current device");
-    const unsigned long long bit = 1ull << (device & 63);
-    if (device < 64 && (devices.load(std::memory_order_acquire) & bit)) return NGP_OK;
-    const void* kernels[2] = {(const void*)k_plan_kinematics, (const void*)k_plan_cost_step};
-    for (const void* k : kernels)
-        if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)NP_LDS) != hipSuccess)
-            return ngp_fail(NGP_ELAUNCH, "plan: cannot raise the dynamic LDS limit");
-    devices.fetch_or(bit, std::memory_order_release);
+    const int rc = ngp_allow_dynamic_lds(devices, {(const void*)k_plan_kinematics, (const void*)k_plan_cost_step}, NP_LDS);
+    if (rc == NGP_LDS_NO_DEVICE) return ngp_fail(NGP_ELAUNCH, "plan: no current device");
+    if (rc != NGP_LDS_OK) return ngp_fail(NGP_ELAUNCH, "plan: cannot raise the dynamic LDS limit");
     return NGP_OK;
 }
 
@@ -588,13 +582,11 @@ extern "C" int ngp_plan_epochs(const ngp_nav_field_t* field, const void* prepare
     const int rc = np_fill("plan_epochs", cfg, R, B, A);
     if (rc != NGP_OK) return rc;
     NGP_REQUIRE(states && initial_accel && adam_state && body, "plan_epochs: null pointer");
-    const size_t need = ngp_plan_workspace(R, B);
-    if (!workspace || workspace_bytes < need)
-        return ngp_fail(NGP_EWORKSPACE, "plan_epochs: workspace of %zu bytes, needs ngp_plan_workspace(R, B) = %zu", workspace_bytes, need);
+    const np_ws w = np_layout(R, B, workspace);
+    if (!workspace || workspace_bytes < w.total)
+        return ngp_fail(NGP_EWORKSPACE, "plan_epochs: workspace of %zu bytes, needs ngp_plan_workspace(R, B) = %zu", workspace_bytes, w.total);
     const uint32_t M = A.S * B;
-    float* points = (float*)workspace;
-    float* sigma = (float*)((char*)workspace + np_align(sizeof(float) * 3 * (size_t)M));
-    float* jac = (float*)((char*)sigma + np_align(sizeof(float) * (size_t)M));
+    float* points = w.points, *sigma = w.sigma, *jac = w.jac;
     {   // the field is checked here, before anything is queued (M = 0 validates and launches nothing)
         const int rc_f = ngp_nav_density_value_jac(field, prepared, points, 0, cfg->rot, sigma, jac, stream);
         if (rc_f != NGP_OK) return rc_f;

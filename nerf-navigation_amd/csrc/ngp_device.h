@@ -10,8 +10,12 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdarg.h>
+#include <math.h>
+#include <atomic>
+#include <initializer_list>
 
 #include "../../include/ngp_hip.h"
+#include "ngp_workspace.h"
 
 // ---------------------------------------------------------------------------
 // host: error reporting
@@ -35,6 +39,31 @@ static inline int ngp_fail(int code, const char* fmt, ...) {
          if (e_ != hipSuccess) return ngp_fail(NGP_ELAUNCH, "%s: %s", name, hipGetErrorString(e_)); } while (0)
 
 static inline uint32_t ngp_div_up(uint64_t a, uint64_t b) { return (uint32_t)((a + b - 1) / b); }
+
+// ---------------------------------------------------------------------------
+// host: launch helpers
+// ---------------------------------------------------------------------------
+
+// More than 64 KiB of dynamic LDS is a per-DEVICE function attribute.  Raises it for `kernels` on the current device, once per device and
+// per call site: `done` is the call site's own static mask of devices 0..63 (one process may drive several); a device beyond that sets the
+// attribute on every call.  A warm call costs hipGetDevice and one atomic load.  The caller words the refusal.
+enum { NGP_LDS_OK = 0, NGP_LDS_NO_DEVICE, NGP_LDS_REFUSED };
+static inline int ngp_allow_dynamic_lds(std::atomic<unsigned long long>& done, std::initializer_list<const void*> kernels, size_t bytes,
+                                        int* device_out = nullptr) {
+    int device = 0;
+    if (hipGetDevice(&device) != hipSuccess || device < 0) return NGP_LDS_NO_DEVICE;
+    if (device_out) *device_out = device;
+    const unsigned long long bit = 1ull << (device & 63);
+    if (device < 64 && (done.load(std::memory_order_acquire) & bit)) return NGP_LDS_OK;
+    for (const void* k : kernels)
+        if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) return NGP_LDS_REFUSED;
+    done.fetch_or(bit, std::memory_order_release);
+    return NGP_LDS_OK;
+}
+
+// The level table of the multi-resolution grid, on the host as everywhere (gridencoder.cu:126-127): scale = 2^(l S) H - 1, resolution = ceil(scale) + 1
+static inline float ngp_level_scale(uint32_t l, float S, uint32_t H) { return exp2f((float)l * S) * (float)H - 1.0f; }
+static inline uint32_t ngp_level_resolution(float scale) { return (uint32_t)ceilf(scale) + 1u; }
 
 // ---------------------------------------------------------------------------
 // device: scalar helpers
@@ -112,6 +141,30 @@ __device__ __forceinline__ uint32_t ngp_compact3(uint32_t x) {
     x = (x | (x >> 8)) & 0xff0000ffu;
     x = (x | (x >> 16)) & 0x0000ffffu;
     return x;
+}
+
+// block-wide inclusive scan of one uint per thread (NW waves): wave scan by DPP-free shuffles, then wave totals in LDS
+template <uint32_t NW>
+__device__ __forceinline__ uint32_t ngp_block_inclusive_scan(uint32_t v, uint32_t* lds4, uint32_t& block_total) {
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    uint32_t s = v;
+    #pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const uint32_t up = __shfl_up(s, off, 64);
+        if ((int)lane >= off) s += up;
+    }
+    if (lane == 63u) lds4[wave] = s;
+    __syncthreads();
+    uint32_t base = 0, total = 0;
+    #pragma unroll
+    for (uint32_t w = 0; w < NW; w++) {
+        const uint32_t t = lds4[w];
+        if (w < wave) base += t;
+        total += t;
+    }
+    __syncthreads();
+    block_total = total;
+    return s + base;
 }
 
 // PCG-XSH-RR 64/32 with Brown's jump-ahead (reference: raymarching/src/pcg32.h:44-205)

@@ -283,8 +283,8 @@ static inline int rf_fill_params(const char* who, const ngp_field_t* f, rf_param
     P.density_scale = f->density_scale;
     P.inv_b2 = 1.0f / (2.0f * f->bound);
     for (int l = 0; l < RF_L; l++) {
-        P.scale[l] = exp2f((float)l * f->S) * (float)f->H - 1.0f;
-        P.resolution[l] = (uint32_t)ceilf(P.scale[l]) + 1u;
+        P.scale[l] = ngp_level_scale((uint32_t)l, f->S, f->H);
+        P.resolution[l] = ngp_level_resolution(P.scale[l]);
     }
     sh_fill_norm(P.shn);
     return NGP_OK;

@@ -6,7 +6,6 @@
 // N/256 workgroups -- >= 2500 for an 800x800 frame, enough to fill 256 CUs several times over.  The occupancy
 // bitfield (cascade * 128^3 / 8 = 0.5 MB at bound 2) is L2-resident; the kernels are bound by the divergent
 // per-ray loops, not by HBM.
-#include <atomic>
 #include <cstring>
 #include "ngp_march.h"
 
@@ -180,6 +179,13 @@ __global__ __launch_bounds__(RM_BLOCK) void k_rm_build_coarse(const uint8_t* __r
 
 static constexpr size_t RM_COARSE_MAX = 48 * 1024;                     // largest map the march kernels stage in LDS (H = 128: 4 KiB per cascade)
 static constexpr size_t RM_OCC_BYTES = 64;                             // behind the map in the workspace: the occupied box, 7 floats
+
+// workspace of march_rays / march_rays_fill: coarse map of `map_bytes` | occupied box.  The size function reserves the largest map.
+struct rm_march_ws { uint32_t* coarse; float* box; size_t total; };
+static rm_march_ws rm_march_layout(size_t map_bytes, void* base) {
+    ngp_carver c(base);
+    return {c.take<uint32_t>(map_bytes / 4, 1), c.take<float>(RM_OCC_BYTES / 4, 1), c.total()};
+}
 // validation switch (process-wide, default 1): the per-op march kernels stop a ray where it leaves the box of everything occupied; 0 = at its own far
 static std::atomic<int> rm_occ_box_enabled{1};
 extern "C" int ngp_march_set_occupied_box(int enabled) { return rm_occ_box_enabled.exchange(enabled ? 1 : 0, std::memory_order_relaxed); }
@@ -224,15 +230,14 @@ __global__ __launch_bounds__(1024) void k_rm_occupied_box(const uint32_t* __rest
     }
 }
 
-// builds the map into `dst` (device) and points the march arguments at it
-static void rm_attach_coarse(march_args& a, void* dst, hipStream_t s, bool with_box) {
+// builds the map into `dst` (device) and points the march arguments at it; `box` (optional) takes the occupied box
+static void rm_attach_coarse(march_args& a, uint32_t* dst, float* box, hipStream_t s) {
     const uint32_t n_blocks_total = a.C * (a.H * a.H * a.H / 64);
-    hipLaunchKernelGGL(k_rm_build_coarse, dim3(ngp_div_up(n_blocks_total, RM_BLOCK)), dim3(RM_BLOCK), 0, s, a.grid, n_blocks_total, (uint32_t*)dst);
-    a.coarse = (const uint32_t*)dst;
+    hipLaunchKernelGGL(k_rm_build_coarse, dim3(ngp_div_up(n_blocks_total, RM_BLOCK)), dim3(RM_BLOCK), 0, s, a.grid, n_blocks_total, dst);
+    a.coarse = dst;
     a.coarse_words = a.H * a.H * a.H / 64 / 32;
-    // the occupied box (behind the map, RM_OCC_BYTES): one more small launch per call
-    if (with_box && rm_occ_box_enabled.load(std::memory_order_relaxed) && ngp_skip_allowed(a.C, a.H, a.bound)) {
-        float* box = reinterpret_cast<float*>(static_cast<unsigned char*>(dst) + (size_t)a.C * a.coarse_words * 4);
+    // the occupied box: one more small launch per call
+    if (box && rm_occ_box_enabled.load(std::memory_order_relaxed) && ngp_skip_allowed(a.C, a.H, a.bound)) {
         hipLaunchKernelGGL(k_rm_occupied_box, dim3(1), dim3(1024), 0, s, a.coarse, a.coarse_words, a.C, a.H, a.C == 1u ? a.bound : (float)(1u << (a.C - 1u)),
                            2.0f * (a.C == 1u ? a.bound : 1.0f) / (float)(a.H / 4u), box);
         a.occ = box;
@@ -266,30 +271,6 @@ __device__ __forceinline__ float train_t0(const ngp_march_t& m, float near, uint
     return near + m.dt_min * rng.next_float();
 }
 
-// block-wide inclusive scan of one uint per thread (NW waves): wave scan by DPP-free shuffles, then wave totals in LDS
-template <uint32_t NW>
-__device__ __forceinline__ uint32_t block_inclusive_scan(uint32_t v, uint32_t* lds4, uint32_t& block_total) {
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint32_t s = v;
-    #pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t up = __shfl_up(s, off, 64);
-        if ((int)lane >= off) s += up;
-    }
-    if (lane == 63u) lds4[wave] = s;
-    __syncthreads();
-    uint32_t base = 0, total = 0;
-    #pragma unroll
-    for (uint32_t w = 0; w < NW; w++) {
-        const uint32_t t = lds4[w];
-        if (w < wave) base += t;
-        total += t;
-    }
-    __syncthreads();
-    block_total = total;
-    return s + base;
-}
-
 __global__ __launch_bounds__(RM_RAY_BLOCK) void k_march_train_count(march_args a, int* __restrict__ rays,
                                                                 const int* __restrict__ counter,
                                                                 uint32_t* __restrict__ block_sums, float* __restrict__ tbuf) {
@@ -316,7 +297,7 @@ __global__ __launch_bounds__(RM_RAY_BLOCK) void k_march_train_count(march_args a
         if (slot < a.N) rays[3ull * slot + 2] = (int)num_steps;      // stash; the write pass completes the record
     }
     uint32_t total;
-    (void)block_inclusive_scan<RM_RAY_BLOCK / 64>(num_steps, lds4, total);
+    (void)ngp_block_inclusive_scan<RM_RAY_BLOCK / 64>(num_steps, lds4, total);
     if (threadIdx.x == 0) block_sums[blockIdx.x] = total;
 }
 
@@ -486,7 +467,7 @@ __global__ __launch_bounds__(RM_BLOCK) void k_march_train_scan(uint32_t* __restr
         const uint32_t i = i0 + threadIdx.x;
         const uint32_t v = (i < nblocks) ? block_sums[i] : 0u;
         uint32_t total;
-        const uint32_t inc = block_inclusive_scan<RM_BLOCK / 64>(v, lds4, total);
+        const uint32_t inc = ngp_block_inclusive_scan<RM_BLOCK / 64>(v, lds4, total);
         const uint32_t c = carry;
         if (i < nblocks) block_sums[i] = c + inc - v;
         __syncthreads();
@@ -518,7 +499,7 @@ __global__ __launch_bounds__(RM_OFFSETS_BLOCK) void k_march_train_offsets(int* _
         const bool live = n < N && slot < N;
         const uint32_t num_steps = live ? (uint32_t)rays[3ull * slot + 2] : 0u;
         uint32_t total;
-        const uint32_t inc = block_inclusive_scan<RM_OFFSETS_BLOCK / 64>(num_steps, lds4, total);
+        const uint32_t inc = ngp_block_inclusive_scan<RM_OFFSETS_BLOCK / 64>(num_steps, lds4, total);
         const uint32_t c = carry;
         if (live) {
             const uint32_t point_index = c + inc - num_steps;
@@ -567,7 +548,7 @@ __global__ __launch_bounds__(RM_RAY_BLOCK) void k_march_train_write(march_args a
     const bool live = (n < a.N) && (slot < a.N);
     const uint32_t num_steps = live ? (uint32_t)rays[3ull * slot + 2] : 0u;
     uint32_t total;
-    const uint32_t inc = block_inclusive_scan<RM_RAY_BLOCK / 64>(num_steps, lds4, total);
+    const uint32_t inc = ngp_block_inclusive_scan<RM_RAY_BLOCK / 64>(num_steps, lds4, total);
     if (!live) return;
     const uint32_t point_index = block_sums[blockIdx.x] + inc - num_steps;
     rays[3ull * slot] = (int)n;
@@ -646,15 +627,16 @@ static constexpr uint32_t RM_WAVE_PER_RAY_MAX = 1u << 17;      // composite: fro
 // rm_wave_march falls back to: selectable so that tests exercise it on whole scenes)
 extern "C" int ngp_march_set_wave_per_ray(int enabled) { return rm_wave_march_enabled.exchange(enabled < 0 || enabled > 2 ? 1 : enabled, std::memory_order_relaxed); }
 
-static size_t rm_train_ws_base(uint32_t N) { return (sizeof(uint32_t) * ((size_t)ngp_div_up(N ? N : 1, RM_RAY_BLOCK) + 4) + 255) & ~(size_t)255; }
-
-// block sums and bases | room for a coarse occupancy map (built per call: the bitfield changes every 16 steps)
-extern "C" size_t ngp_march_rays_train_workspace(uint32_t N) { return rm_train_ws_base(N) + RM_COARSE_MAX + RM_OCC_BYTES; }
-
-// The same plus room for every sample's t (N * max_steps floats): with it the second pass does not march again.
-extern "C" size_t ngp_march_rays_train_workspace_full(uint32_t N, uint32_t max_steps) {
-    return ngp_march_rays_train_workspace(N) + sizeof(float) * (size_t)N * max_steps;
+// block sums and bases | room for a coarse occupancy map (built per call: the bitfield changes every 16 steps) and its box | optional: every
+// sample's t (N * max_steps floats; with it the second pass does not march again)
+struct rm_train_ws { uint32_t* block_sums; uint32_t* bases; uint32_t* coarse; size_t total; float* tbuf; size_t total_full; };
+static rm_train_ws rm_train_layout(uint32_t N, uint32_t max_steps, void* base) {
+    ngp_carver c(base);
+    return {c.take<uint32_t>(ngp_div_up(N ? N : 1, RM_RAY_BLOCK), 1), c.take<uint32_t>(4, 1), c.take<uint32_t>((RM_COARSE_MAX + RM_OCC_BYTES) / 4), c.total(),
+            c.take<float>((size_t)N * max_steps, 1), c.total()};
 }
+extern "C" size_t ngp_march_rays_train_workspace(uint32_t N) { return rm_train_layout(N, 0, nullptr).total; }
+extern "C" size_t ngp_march_rays_train_workspace_full(uint32_t N, uint32_t max_steps) { return rm_train_layout(N, max_steps, nullptr).total_full; }
 
 static int rm_march_rays_train(const float* rays_o, const float* rays_d, const uint8_t* grid, float bound, float dt_gamma,
                                uint32_t max_steps, uint32_t N, uint32_t C, uint32_t H, uint32_t M,
@@ -673,20 +655,18 @@ static int rm_march_rays_train(const float* rays_o, const float* rays_d, const u
     NGP_REQUIRE(rays_o && rays_d && grid && nears && fars && xyzs && dirs && deltas && rays && counter, "march_rays_train: null pointer");
     NGP_REQUIRE(C >= 1 && C <= 16 && H >= 1 && H <= 1024 && max_steps >= 1, "march_rays_train: bad C/H/max_steps");
     NGP_REQUIRE((H & (H - 1u)) == 0u, "march_rays_train: the grid size must be a power of two (cells are addressed by Morton index: beyond H^3 otherwise)");
-    NGP_REQUIRE(workspace && workspace_bytes >= ngp_march_rays_train_workspace(N), "march_rays_train: workspace too small");
-    if (N == 0) return NGP_OK;
+    const rm_train_ws w = rm_train_layout(N, max_steps, workspace);
+    NGP_REQUIRE(workspace && workspace_bytes >= w.total, "march_rays_train: workspace too small");
     const uint32_t nblocks = ngp_div_up(N, RM_RAY_BLOCK);
-    uint32_t* block_sums = (uint32_t*)workspace;
-    uint32_t* bases = block_sums + nblocks;
+    uint32_t* block_sums = w.block_sums;
+    uint32_t* bases = w.bases;
     march_args a{rays_o, rays_d, grid, nears, fars, bound, dt_gamma, max_steps, N, C, H, M, perturb};
     hipStream_t s = (hipStream_t)stream;
-    float* tbuf = nullptr;
-    if (workspace_bytes >= ngp_march_rays_train_workspace_full(N, max_steps))
-        tbuf = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(workspace) + ngp_march_rays_train_workspace(N));
+    float* tbuf = workspace_bytes >= w.total_full ? w.tbuf : nullptr;
     const size_t cbytes = rm_coarse_bytes(grid, C, H);
     // (no occupied box for the training march: a training batch's rays mostly end inside the learned grid's box, the wave-per-ray count pass crosses what is
     //  left in 64-point windows, and the extra launch and per-ray slab test cost more than they save: 0.872 against 0.846 ms per step, measured)
-    if (cbytes) rm_attach_coarse(a, reinterpret_cast<unsigned char*>(workspace) + rm_train_ws_base(N), s, false);
+    if (cbytes) rm_attach_coarse(a, w.coarse, nullptr, s);
     // one wave per ray when the lattice is closed-form (constant step) and the sample parameters can be recorded; else one lane per ray
     const int wave_mode = rm_wave_march_enabled.load(std::memory_order_relaxed);
     const bool wave_per_ray = tbuf && cbytes && dt_gamma == 0.0f && C <= 4 && wave_mode != 0;
@@ -1259,8 +1239,9 @@ static int march_rays_launch(bool fill, uint32_t M, uint32_t n_alive, uint32_t n
     // the coarse map pays when rays cross empty space; it is rebuilt on every call (2 us: the bitfield may have changed, and a cache
     // keyed on a pointer could go stale silently)
     const size_t cbytes = (workspace && n_alive) ? rm_coarse_bytes(grid, C, H) : 0;
-    const size_t lds = (cbytes && workspace_bytes >= cbytes + RM_OCC_BYTES) ? cbytes : 0;
-    if (lds) rm_attach_coarse(a, workspace, (hipStream_t)stream, true);
+    const rm_march_ws w = rm_march_layout(cbytes, workspace);
+    const size_t lds = (cbytes && workspace_bytes >= w.total) ? cbytes : 0;
+    if (lds) rm_attach_coarse(a, w.coarse, w.box, (hipStream_t)stream);
     const bool big = n_alive >= 65536u;          // (measured: the frame takes the same time with 64-thread workgroups throughout; 256 stage the map 4x less often)
     const uint32_t bs = big ? RM_BLOCK : RM_RAY_BLOCK;
     const dim3 grid_dim(ngp_div_up(n_alive ? n_alive : 1, bs)), block(bs);
@@ -1290,7 +1271,7 @@ extern "C" int ngp_march_rays_fill(uint32_t n_alive, uint32_t n_step, const int3
                              xyzs, dirs, deltas, perturb, workspace, workspace_bytes, stream);
 }
 
-extern "C" size_t ngp_march_rays_workspace(uint32_t C, uint32_t H) { (void)C; (void)H; return RM_COARSE_MAX + RM_OCC_BYTES; }
+extern "C" size_t ngp_march_rays_workspace(uint32_t C, uint32_t H) { (void)C; (void)H; return rm_march_layout(RM_COARSE_MAX, nullptr).total; }
 
 extern "C" int ngp_composite_rays(uint32_t n_alive, uint32_t n_step, int32_t* rays_alive, float* rays_t, const float* sigmas,
                                   const float* rgbs, const float* deltas, float* weights_sum, float* depth, float* image, void* stream) {
@@ -1367,17 +1348,17 @@ __global__ __launch_bounds__(RM_BLOCK) void k_compact_write(const int* __restric
     }
 }
 
-extern "C" size_t ngp_compact_alive_workspace(uint32_t n_alive) {
-    return sizeof(uint32_t) * ((size_t)ngp_div_up(n_alive ? n_alive : 1, RM_BLOCK) + 4);
-}
+static ngp_array_ws<uint32_t> rm_compact_layout(uint32_t n_alive, void* base) { return ngp_array_layout<uint32_t>((size_t)ngp_div_up(n_alive ? n_alive : 1, RM_BLOCK) + 4, base); }
+extern "C" size_t ngp_compact_alive_workspace(uint32_t n_alive) { return rm_compact_layout(n_alive, nullptr).total; }
 
 static int rm_compact_alive(const int32_t* rays_alive, uint32_t n_alive, int32_t* out, int32_t* n_out, int32_t* host_pair, int32_t seq,
                             void* workspace, size_t workspace_bytes, void* stream) {
     NGP_REQUIRE(rays_alive && out && n_out, "compact_alive: null pointer");
-    NGP_REQUIRE(workspace && workspace_bytes >= ngp_compact_alive_workspace(n_alive), "compact_alive: workspace too small");
+    const auto w = rm_compact_layout(n_alive, workspace);
+    NGP_REQUIRE(workspace && workspace_bytes >= w.total, "compact_alive: workspace too small");
     hipStream_t s = (hipStream_t)stream;
     const uint32_t nblocks = ngp_div_up(n_alive ? n_alive : 1, RM_BLOCK);
-    uint32_t* block_sums = (uint32_t*)workspace;
+    uint32_t* block_sums = w.p;
     hipLaunchKernelGGL(k_compact_count, dim3(nblocks), dim3(RM_BLOCK), 0, s, rays_alive, n_alive, block_sums);
     hipLaunchKernelGGL(k_compact_write, dim3(nblocks), dim3(RM_BLOCK), 0, s, rays_alive, n_alive, block_sums, out, n_out, host_pair, seq);
     NGP_CHECK_LAUNCH("compact_alive");

@@ -23,7 +23,6 @@
 // Semantics vs the reference loop (DESIGN.md "Fused path"): each ray is marched by a single resumable march from
 // `near` (the reference re-enters march_rays every n_step samples); a ray consumes at most max_steps samples (the
 // reference offers between max_steps and max_steps+7 depending on the schedule; such rays are counted in stats[1]).
-#include <atomic>
 #include "ngp_mlp.h"
 #include "ngp_sh.h"
 #include "ngp_field.h"
@@ -853,17 +852,24 @@ static std::atomic<int> rv_tile_order_enabled{1};
 // validation switch: 0 = every band's tiles in row-major order; results are identical either way
 extern "C" int ngp_render_set_tile_order(int enabled) { return rv_tile_order_enabled.exchange(enabled ? 1 : 0, std::memory_order_relaxed); }
 
-// header: debug words (RV_COUNTERS builds) | extent of the occupied blocks (words 26..31) | band queues (words 32..63)
-// The coarse map takes at most the LDS left beside the rest of the frame kernel's carve (< 12 KiB), so the end of its 48 KiB region holds the
-// RV_TIMELINE build's histogram (RV_WS_HIST, 8 KiB).
-static constexpr size_t RV_WS_COARSE = 256, RV_WS_HIST = RV_WS_COARSE + 36 * 1024, RV_WS_AREA = 256 + 48 * 1024;
-static_assert(RV_LDS_W + RV_LDS_SH + RV_LDS_LV + RV_LDS_SMP + 36 * 1024 > 160 * 1024, "the coarse map could reach RV_WS_HIST");
-static_assert(RV_WS_HIST + 2048 * sizeof(uint32_t) <= RV_WS_AREA, "workspace carve");
-extern "C" size_t ngp_render_frame_workspace(uint32_t N) {
-    // header | coarse occupancy map (<= 48 KiB) | an area of two u32 per 64 rays: the tile order (queue position -> tile, then each tile's estimated
-    // cost).  The size is part of the C ABI (callers allocate it; the cameras of ngp_render_frames_camera follow it).
-    return RV_WS_AREA + 2 * sizeof(uint32_t) * (size_t)ngp_div_up(N, 64u);
+// Frame workspace: header (64 words: debug words of RV_COUNTERS builds | extent of the occupied blocks, words 26..31 | band queues, words 32..63) |
+// coarse occupancy map | the RV_TIMELINE build's histogram (8 KiB used) | tile order: queue position -> tile, then each tile's estimated cost, one u32
+// per 64 rays each | the cameras of ngp_render_frames_camera, 256-byte aligned.  The coarse map takes at most the LDS left beside the rest of the frame
+// kernel's carve (< 12 KiB), so it never reaches the histogram.  The sizes are part of the C ABI (callers allocate them).
+static constexpr size_t RV_WS_HEADER_WORDS = 64, RV_WS_COARSE_BYTES = 36 * 1024, RV_WS_HIST_WORDS = 2048, RV_WS_HIST_BYTES = 12 * 1024;
+static_assert(RV_LDS_W + RV_LDS_SH + RV_LDS_LV + RV_LDS_SMP + RV_WS_COARSE_BYTES > 160 * 1024, "the coarse map could reach the histogram");
+static_assert(RV_WS_HIST_WORDS * sizeof(uint32_t) <= RV_WS_HIST_BYTES, "workspace carve");
+struct rv_ws {                                         // frame_total: without the cameras
+    uint32_t* header; uint32_t* occ_ext; uint32_t* queues; uint32_t* coarse; uint32_t* hist; uint32_t* perm; uint32_t* cost; size_t frame_total; ngp_camera* cams; size_t total;
+};
+static rv_ws rv_layout(uint32_t N, uint32_t n_cams, void* base) {
+    const size_t n64 = ngp_div_up(N, 64u);
+    ngp_carver c(base);
+    return {c.take<uint32_t>(26, 1), c.take<uint32_t>(6, 1), c.take<uint32_t>(32, 1), c.take<uint32_t>(RV_WS_COARSE_BYTES / 4, 1), c.take<uint32_t>(RV_WS_HIST_BYTES / 4, 1),
+            c.take<uint32_t>(n64, 1), c.take<uint32_t>(n64, 1), c.total(), c.take<ngp_camera>(n_cams), c.total()};
 }
+static_assert(RV_BANDS <= 32 && 26 + 6 + 32 == RV_WS_HEADER_WORDS, "workspace header");
+extern "C" size_t ngp_render_frame_workspace(uint32_t N) { return rv_layout(N, 0, nullptr).frame_total; }
 
 static int rv_fill_camera(const char* who, const float* pose_host, const float* intrinsics_host, uint32_t H, uint32_t W, ngp_camera& cam) {
     NGP_REQUIRE(pose_host && intrinsics_host, "camera: pose / intrinsics are host pointers and must not be null");
@@ -887,14 +893,15 @@ static int rv_render_frame(const ngp_field_t* field_host, const float* rays_o, c
     rf_params P;
     int rc = rf_fill_params("render_frame", field_host, P);
     if (rc != NGP_OK) return rc;
-    NGP_REQUIRE(stats && workspace && workspace_bytes >= RV_WS_COARSE, "render_frame: stats / workspace missing");
+    const rv_ws ws = rv_layout(N, cam && n_cams > 1 ? n_cams : 0u, workspace);
+    NGP_REQUIRE(stats && workspace && ngp_ws_holds(workspace, workspace_bytes, ws.header, RV_WS_HEADER_WORDS * 4), "render_frame: stats / workspace missing");
     NGP_REQUIRE(aabb_host && bg_color3_host, "render_frame: aabb / bg_color are host pointers and must not be null");
     NGP_REQUIRE(C >= 1 && C <= 16 && Hgrid >= 1 && Hgrid <= 1024 && max_steps >= 1, "render_frame: bad C/H/max_steps");
     // cells are addressed by Morton index: for a grid size that is not a power of two the index of a cell can lie beyond H^3 (H = 48: cell (47, 47, 47) has
     // index 2^18 - 1 > 48^3), i.e. beyond the end of the bitfield
     NGP_REQUIRE(rv_pow2(Hgrid), "render_frame: the grid size must be a power of two (cells are addressed by Morton index)");
     hipStream_t s = (hipStream_t)stream;
-    if (hipMemsetAsync(stats, 0, 4 * sizeof(uint32_t), s) != hipSuccess || hipMemsetAsync(workspace, 0, RV_WS_COARSE, s) != hipSuccess)
+    if (hipMemsetAsync(stats, 0, 4 * sizeof(uint32_t), s) != hipSuccess || hipMemsetAsync(ws.header, 0, RV_WS_HEADER_WORDS * 4, s) != hipSuccess)
         return ngp_fail(NGP_ELAUNCH, "render_frame: memset failed");
     if (N == 0) return NGP_OK;
     NGP_REQUIRE((cam || (rays_o && rays_d)) && bitfield && image && depth && weights_sum, "render_frame: null pointer");
@@ -903,10 +910,9 @@ static int rv_render_frame(const ngp_field_t* field_host, const float* rays_o, c
     F.cam = cam ? *cam : ngp_camera{};
     F.cams = nullptr; F.frame_rays = N;
     if (cam && n_cams > 1) {
-        // the cameras travel in the workspace, behind the coarse occupancy map and the reserved area (pageable host memory: the copy is staged before the call returns)
-        const size_t at = (ngp_render_frame_workspace(N) + 255) & ~(size_t)255;
-        NGP_REQUIRE(workspace_bytes >= at + n_cams * sizeof(ngp_camera), "render_frames_camera: workspace too small (ngp_render_frames_workspace)");
-        ngp_camera* dst = reinterpret_cast<ngp_camera*>(reinterpret_cast<unsigned char*>(workspace) + at);
+        // the cameras travel in the workspace, behind the tile order (pageable host memory: the copy is staged before the call returns)
+        NGP_REQUIRE(workspace_bytes >= ws.total, "render_frames_camera: workspace too small (ngp_render_frames_workspace)");
+        ngp_camera* dst = ws.cams;
         if (hipMemcpyAsync(dst, cam, n_cams * sizeof(ngp_camera), hipMemcpyHostToDevice, s) != hipSuccess) return ngp_fail(NGP_ELAUNCH, "render_frames_camera: camera copy failed");
         F.cams = dst; F.frame_rays = N / n_cams;
     }
@@ -915,13 +921,13 @@ static int rv_render_frame(const ngp_field_t* field_host, const float* rays_o, c
     F.dt_gamma = dt_gamma; F.max_steps = max_steps;
     for (int i = 0; i < 3; i++) F.bg[i] = bg_color3_host[i];
     F.image = image; F.depth = depth; F.weights_sum = weights_sum;
-    F.stats = stats; F.queue = (uint32_t*)workspace;
+    F.stats = stats; F.queue = ws.header;
 #ifdef RV_COUNTERS
     F.hist = nullptr;
 #ifdef RV_TIMELINE                                      // the timeline's atomics perturb the cycle counters: a build of its own
-    if (workspace_bytes >= RV_WS_HIST + 2048 * sizeof(uint32_t)) {
-        F.hist = reinterpret_cast<uint32_t*>(reinterpret_cast<unsigned char*>(workspace) + RV_WS_HIST);
-        if (hipMemsetAsync(F.hist, 0, 2048 * sizeof(uint32_t), s) != hipSuccess) return ngp_fail(NGP_ELAUNCH, "render_frame: memset failed");
+    if (ngp_ws_holds(workspace, workspace_bytes, ws.hist, RV_WS_HIST_WORDS * sizeof(uint32_t))) {
+        F.hist = ws.hist;
+        if (hipMemsetAsync(F.hist, 0, RV_WS_HIST_WORDS * sizeof(uint32_t), s) != hipSuccess) return ngp_fail(NGP_ELAUNCH, "render_frame: memset failed");
     }
 #endif
 #endif
@@ -934,25 +940,23 @@ static int rv_render_frame(const ngp_field_t* field_host, const float* rays_o, c
     F.tile_perm = nullptr;
     static_assert(sizeof(rf_lane_levels) * 4 == RV_LDS_LV, "LDS carve of the level table");
     size_t lds = RV_LDS_W + RV_LDS_SH + RV_LDS_LV + RV_LDS_SMP;
-    const void* kernel = reinterpret_cast<const void*>(k_render_frame_multi);
     const uint64_t blocks_per_level = (uint64_t)Hgrid * Hgrid * Hgrid / 64;
     const uint64_t coarse_bytes = (uint64_t)C * blocks_per_level / 8;
     // (C * H^3 <= 2^24: the reference forms the cell index in binary32, raymarching.cu:783; beyond that it rounds)
     // and the map has to fit in the LDS left beside the weights, SH and sample slots (8 KiB for 2 cascades of 128^3; from 3
     // cascades on it does not: such a frame is marched without the map, i.e. cell by cell through the bitfield itself)
     if (rv_pow2(Hgrid) && Hgrid >= 8 && blocks_per_level % 32 == 0 && lds + coarse_bytes <= 160 * 1024 && (uint64_t)C * Hgrid * Hgrid * Hgrid <= (1ull << 24) &&
-        workspace_bytes >= RV_WS_COARSE + coarse_bytes && (reinterpret_cast<uintptr_t>(bitfield) & 7u) == 0) {
-        uint32_t* coarse = reinterpret_cast<uint32_t*>(reinterpret_cast<unsigned char*>(workspace) + RV_WS_COARSE);
+        ngp_ws_holds(workspace, workspace_bytes, ws.coarse, coarse_bytes) && (reinterpret_cast<uintptr_t>(bitfield) & 7u) == 0) {
+        uint32_t* coarse = ws.coarse;
         const uint32_t n_blocks_total = (uint32_t)(C * blocks_per_level);
         F.coarse = coarse;
         F.coarse_words = (uint32_t)(blocks_per_level / 32);
         lds += coarse_bytes;
         // block skipping and the occupied box need the cascades nested in powers of two (see below)
         uint32_t* ext = nullptr;
-        int e2;
-        const bool nested = Hgrid >= 64 && (C == 1 || frexpf(field_host->bound, &e2) == 0.5f);
+        const bool nested = ngp_skip_allowed(C, Hgrid, field_host->bound);
         if (nested && rv_occ_box_enabled.load(std::memory_order_relaxed) && lds + 32 <= 160 * 1024) {
-            ext = reinterpret_cast<uint32_t*>(workspace) + 26;          // header words 26..31 (zeroed above)
+            ext = ws.occ_ext;                                           // header words 26..31 (zeroed above)
             F.occ_ext = ext;
             F.occ_top = C == 1 ? field_host->bound : (float)(1u << (C - 1));
             F.occ_unit = 2.0f * (C == 1 ? field_host->bound : 1.0f) / (float)(Hgrid / 4);
@@ -962,17 +966,15 @@ static int rv_render_frame(const ngp_field_t* field_host, const float* rays_o, c
                            (uint32_t)blocks_per_level, C, ext);
         // block skipping needs the 16^3 blocks aligned with the cascade boundaries (cells H/4 and 3H/4 of the next level) and
         // every level's half-width a power of two: H a power of two >= 64, and bound a power of two unless there is one cascade
-        int e;
-        F.skip = (rv_block_skip_enabled.load(std::memory_order_relaxed) && Hgrid >= 64 && (C == 1 || frexpf(field_host->bound, &e) == 0.5f)) ? 1u : 0u;
+        F.skip = (rv_block_skip_enabled.load(std::memory_order_relaxed) && nested) ? 1u : 0u;
     }
-    // tile order: estimate every tile's cost from the coarse map and sort each band's tiles by it (k_tile_cost, k_tile_sort: the permutation, then
-    // the costs, in the reserved area behind the coarse map)
+    // tile order: estimate every tile's cost from the coarse map and sort each band's tiles by it (k_tile_cost, k_tile_sort)
     // (not for several frames per launch: their drain is shared by all of them, and the estimate of 8 frames took longer than it saved)
     const uint32_t n_tiles = F.tile_w ? N / 64u : 0u;
     if (n_tiles && !F.cams && F.coarse && rv_tile_order_enabled.load(std::memory_order_relaxed) && ngp_div_up(n_tiles, RV_BANDS) <= RV_ORDER_MAX &&
-        workspace_bytes >= RV_WS_AREA + 2 * sizeof(uint32_t) * (size_t)n_tiles) {
-        uint32_t* perm = reinterpret_cast<uint32_t*>(reinterpret_cast<unsigned char*>(workspace) + RV_WS_AREA);
-        uint32_t* cost = perm + n_tiles;
+        workspace_bytes >= ws.frame_total) {
+        uint32_t* perm = ws.perm;
+        uint32_t* cost = ws.cost;
         hipLaunchKernelGGL(k_tile_cost, dim3(ngp_div_up(n_tiles, 4u)), dim3(256), 0, s, F, P.bound, n_tiles, cost);
         hipLaunchKernelGGL(k_tile_sort, dim3(RV_BANDS), dim3(1024), 0, s, cost, n_tiles, perm);
         NGP_CHECK_LAUNCH("render_frame: tile order");
@@ -981,14 +983,9 @@ static int rv_render_frame(const ngp_field_t* field_host, const float* rays_o, c
     NGP_REQUIRE(lds <= 160 * 1024, "render_frame: LDS carve exceeds 160 KiB");
     // the raised dynamic-LDS limit is a per-device function attribute: set it once on every device this process renders on
     static std::atomic<unsigned long long> attr_devices{0};
-    int device = 0;
-    if (hipGetDevice(&device) != hipSuccess || device < 0) return ngp_fail(NGP_ELAUNCH, "render_frame: no current device");
-    const unsigned long long device_bit = 1ull << (device & 63);
-    if (device >= 64 || !(attr_devices.load(std::memory_order_acquire) & device_bit)) {
-        if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-            return ngp_fail(NGP_ELAUNCH, "render_frame: cannot raise the dynamic LDS limit");
-        attr_devices.fetch_or(device_bit, std::memory_order_release);
-    }
+    const int rc_lds = ngp_allow_dynamic_lds(attr_devices, {reinterpret_cast<const void*>(k_render_frame_multi)}, 160 * 1024);
+    if (rc_lds == NGP_LDS_NO_DEVICE) return ngp_fail(NGP_ELAUNCH, "render_frame: no current device");
+    if (rc_lds != NGP_LDS_OK) return ngp_fail(NGP_ELAUNCH, "render_frame: cannot raise the dynamic LDS limit");
     // persistent grid: RV_BLOCKS_PER_CU workgroups per CU, fewer when the frame is small
     uint32_t blocks = 256 * RV_BLOCKS_PER_CU;
     const uint32_t need = ngp_div_up(N, RV_BLOCK);
@@ -1025,9 +1022,7 @@ extern "C" int ngp_render_frame_camera(const ngp_field_t* field_host, const floa
 // ramp (256 workgroups staging 36 KiB of weights, the first tiles marching) and drain (the last waves finishing alone) are paid once per
 // launch instead of once per frame: the same pixels, bit for bit, as P calls of ngp_render_frame_camera.  H and W must be multiples of 8
 // (an 8x8 tile then never straddles two frames).  Workspace: ngp_render_frames_workspace(P, H * W).
-extern "C" size_t ngp_render_frames_workspace(uint32_t P, uint32_t rays_per_frame) {
-    return ((ngp_render_frame_workspace(P * rays_per_frame) + 255) & ~(size_t)255) + (size_t)P * sizeof(ngp_camera);
-}
+extern "C" size_t ngp_render_frames_workspace(uint32_t P, uint32_t rays_per_frame) { return rv_layout(P * rays_per_frame, P, nullptr).total; }
 
 extern "C" int ngp_render_frames_camera(const ngp_field_t* field_host, const float* poses_host, uint32_t P, const float* intrinsics_host, uint32_t H, uint32_t W,
                                         const float* aabb_host, float min_near, const uint8_t* bitfield, uint32_t C, uint32_t Hgrid,

@@ -166,6 +166,14 @@ __global__ __launch_bounds__(TH_BLOCK) void k_train_head_direct(const float* __r
     *ticket = 0u;
 }
 
+// workspace of the two loss heads: ticket (zero before the first call; the last workgroup puts the zero back) | one partial sum per workgroup
+struct th_ws { uint32_t* ticket; float* partial; size_t total; };
+static th_ws th_layout(void* base) {
+    ngp_carver c(base);
+    return {c.take<uint32_t>(1, 1), c.take<float>(TH_MAX_BLOCKS, 1), c.total()};
+}
+extern "C" size_t ngp_mse_head_workspace(void) { return th_layout(nullptr).total; }
+
 extern "C" int ngp_train_head_direct(const float* weights_sum, const float* image, const float* bg, uint32_t bg_rows, float bg_value, const float* target,
                                      const float* scale, uint32_t N, float* out_image, float* loss, float* grad_image, float* grad_weights_sum,
                                      void* const* zero_ptrs, const uint64_t* zero_bytes, uint32_t zero_count, void* workspace, size_t workspace_bytes, void* stream) {
@@ -173,7 +181,8 @@ extern "C" int ngp_train_head_direct(const float* weights_sum, const float* imag
     NGP_REQUIRE(weights_sum && image && target && out_image && loss && grad_image && grad_weights_sum && workspace, "train_head_direct: null pointer");
     NGP_REQUIRE(bg_rows == 0 || ((bg_rows == 1 || bg_rows == N) && bg), "train_head_direct: bg_rows must be 0 (bg_value), 1 (bg[3]) or N (bg[N,3])");
     NGP_REQUIRE(zero_count <= 3 && (zero_count == 0 || (zero_ptrs && zero_bytes)), "train_head_direct: at most three buffers to clear");
-    if (workspace_bytes < (size_t)(1 + TH_MAX_BLOCKS) * 4) return ngp_fail(NGP_EWORKSPACE, "train_head_direct: workspace of %zu bytes, %zu needed", workspace_bytes, (size_t)(1 + TH_MAX_BLOCKS) * 4);
+    const th_ws w = th_layout(workspace);
+    if (workspace_bytes < w.total) return ngp_fail(NGP_EWORKSPACE, "train_head_direct: workspace of %zu bytes, %zu needed", workspace_bytes, w.total);
     th_zero Z{{nullptr, nullptr, nullptr}, {0, 0, 0}};
     uint64_t most = 0;
     for (uint32_t z = 0; z < zero_count; z++) {
@@ -188,9 +197,8 @@ extern "C" int ngp_train_head_direct(const float* weights_sum, const float* imag
     uint32_t blocks = ngp_div_up(most, (uint64_t)TH_BLOCK * 16 * 8);       // ~8 16-byte stores per thread of the clearing loop
     if (blocks > 2048u) blocks = 2048u;
     if (blocks < loss_blocks) blocks = loss_blocks;
-    uint32_t* ticket = (uint32_t*)workspace;
     hipLaunchKernelGGL(k_train_head_direct, dim3(blocks), dim3(TH_BLOCK), 0, (hipStream_t)stream, weights_sum, image, bg, bg_rows, bg_value, target, scale, N,
-                       loss_blocks, per_block, out_image, loss, grad_image, grad_weights_sum, ticket, (float*)(ticket + 1), Z);
+                       loss_blocks, per_block, out_image, loss, grad_image, grad_weights_sum, w.ticket, w.partial, Z);
     NGP_CHECK_LAUNCH("train_head_direct");
     return NGP_OK;
 }
@@ -218,19 +226,16 @@ extern "C" int ngp_train_mix_backward(const float* grad_out_image, const float* 
     return NGP_OK;
 }
 
-extern "C" size_t ngp_mse_head_workspace(void) { return (size_t)(1 + TH_MAX_BLOCKS) * 4; }
-
 extern "C" int ngp_mse_head_forward(const float* pred, const float* target, uint32_t numel, const float* scale, float* loss, float* grad_unit,
                                     void* workspace, size_t workspace_bytes, void* stream) {
     NGP_REQUIRE(numel >= 1, "mse_head_forward: empty input (torch's mean of nothing is NaN; callers decide)");
     NGP_REQUIRE(pred && target && loss && grad_unit && workspace, "mse_head_forward: null pointer");
-    if (workspace_bytes < ngp_mse_head_workspace()) return ngp_fail(NGP_EWORKSPACE, "mse_head_forward: workspace of %zu bytes, %zu needed", workspace_bytes, ngp_mse_head_workspace());
+    const th_ws w = th_layout(workspace);
+    if (workspace_bytes < w.total) return ngp_fail(NGP_EWORKSPACE, "mse_head_forward: workspace of %zu bytes, %zu needed", workspace_bytes, w.total);
     uint32_t blocks = ngp_div_up(numel, TH_SLICE);
     if (blocks > TH_MAX_BLOCKS) blocks = TH_MAX_BLOCKS;
     const uint32_t per_block = ngp_div_up(numel, blocks);
-    uint32_t* ticket = (uint32_t*)workspace;
-    hipLaunchKernelGGL(k_mse_head_fwd, dim3(blocks), dim3(TH_BLOCK), 0, (hipStream_t)stream, pred, target, numel, per_block, scale, loss, grad_unit, ticket,
-                       (float*)(ticket + 1));
+    hipLaunchKernelGGL(k_mse_head_fwd, dim3(blocks), dim3(TH_BLOCK), 0, (hipStream_t)stream, pred, target, numel, per_block, scale, loss, grad_unit, w.ticket, w.partial);
     NGP_CHECK_LAUNCH("mse_head_forward");
     return NGP_OK;
 }
