@@ -811,7 +811,12 @@ __global__ __launch_bounds__(1024) void k_gs_bin(const _Float16* __restrict__ gr
     const uint32_t side = align_corners ? resolution : resolution + 1u;
     const uint32_t s1 = side, s2 = side * side;
     const bool idx_dense = (uint64_t)side * side * side <= (uint64_t)level_rows;           // every stride fits: x + y s1 + z s2 < rows, no modulo
-    const bool idx_pow2 = !idx_dense && gridtype == 0 && (level_rows & (level_rows - 1u)) == 0;   // hashed, 2^k rows: the modulo is a mask
+    // whether get_grid_index hashes is decided by ITS stride, a 32-bit product: from a side of 2^16 on (per_level_scale 2 from resolution 16: levels 12-15) it
+    // wraps to a small number, the reference then does not hash the level, and neither may this kernel (ge_index below repeats the wrapped strides)
+    uint32_t stride = 1;
+    #pragma unroll
+    for (uint32_t d = 0; d < D; d++) if (stride <= level_rows) stride *= side;
+    const bool idx_pow2 = !idx_dense && gridtype == 0 && stride > level_rows && (level_rows & (level_rows - 1u)) == 0;   // hashed, 2^k rows: the modulo is a mask
     __syncthreads();                                   // s_hist is zero
 
     uint32_t e_val[8], e_key[8], e_rank[8];

@@ -73,17 +73,16 @@ def _half_table(embeddings, training):
     return half
 
 
-_MAX_ROWS = {}
-
-
 def offsets_info(offsets):
-    """(largest number of rows of any level, rows of the whole table, the offsets as a list): one host read per offsets tensor, cached on its
-    storage pointer"""
-    key = (offsets.data_ptr(), offsets.numel(), str(offsets.device))
-    if key not in _MAX_ROWS:
+    """(largest number of rows of any level, rows of the whole table, the offsets as a list): one host read per offsets tensor, kept ON the tensor.
+    (It used to be a dictionary keyed by the storage address, which outlives the tensor: the allocator hands a freed address to the next encoder's
+    offsets, and that encoder then got the row count of the old one -- a table gradient of the wrong size that the binned scatter wrote past.)"""
+    c = getattr(offsets, "_ngp_info", None)
+    if c is None or c[0] != offsets._version or c[1] != offsets.data_ptr():
         o = offsets.detach().cpu().to(torch.int64)
-        _MAX_ROWS[key] = (int((o[1:] - o[:-1]).max()), int(o[-1]), [int(v) for v in o])
-    return _MAX_ROWS[key]
+        c = (offsets._version, offsets.data_ptr(), (int((o[1:] - o[:-1]).max()), int(o[-1]), [int(v) for v in o]))
+        offsets._ngp_info = c
+    return c[2]
 
 
 def offsets_max_rows(offsets):
