@@ -160,7 +160,9 @@ __global__ __launch_bounds__(256) void k_ft_encode_levels(rf_params P, const flo
     #pragma unroll
     for (int d = 0; d < 3; d++)
         if (stride <= size) { if (d == 1) s1 = stride; if (d == 2) s2 = stride; stride *= side; }
-    const bool dense = stride <= size;
+    const bool dense = stride <= size;                                     // the reference's decision, from its 32-bit stride product
+    // from a side of 2^16 on that product wraps: the reference still indexes the level, with the wrapped strides, modulo its size (rf_setup_levels)
+    const bool wrapped = dense && (uint64_t)side * side * side > (uint64_t)size;
     const bool pow2 = (size & (size - 1u)) == 0u;
     const uint32_t* tab = P.table + o0;
 
@@ -183,10 +185,14 @@ __global__ __launch_bounds__(256) void k_ft_encode_levels(rf_params P, const flo
             pg[d] = (uint32_t)fl;
             f[q][d] = p - fl;
         }
-        if (dense) {                                                       // x + y s1 + z s2 < size by construction
+        if (dense) {                                                       // x + y s1 + z s2 < size by construction, unless the strides wrapped
             const uint32_t i0 = pg[0] + pg[1] * s1 + pg[2] * s2;
             #pragma unroll
-            for (int c = 0; c < 8; c++) raw[q][c] = tab[i0 + (c & 1) + ((c & 2) ? s1 : 0u) + ((c & 4) ? s2 : 0u)];
+            for (int c = 0; c < 8; c++) {
+                uint32_t idx = i0 + (c & 1) + ((c & 2) ? s1 : 0u) + ((c & 4) ? s2 : 0u);
+                if (wrapped) idx = pow2 ? (idx & (size - 1u)) : (idx % size);      // (wave-uniform)
+                raw[q][c] = tab[idx];
+            }
         } else {
             constexpr uint32_t P1 = 2654435761u, P2 = 805459861u;          // fast_hash (gridencoder.cu:35-51)
             const uint32_t hy[2] = {pg[1] * P1, (pg[1] + 1u) * P1}, hz[2] = {pg[2] * P2, (pg[2] + 1u) * P2};

@@ -41,7 +41,7 @@ struct rf_lane_levels {
     float scale[4];
     uint32_t base4[4];                         // byte offset of the level's first row in the table
     uint32_t size[4];                          // rows
-    uint32_t s1b[4], s2b[4];                   // dense level: y and z strides in BYTES; s1b == 0 marks a hashed level
+    uint32_t s1b[4], s2b[4];                   // dense level: y and z strides in BYTES; s1b == 0 marks a hashed level, bit 0 of s1b one indexed with wrapped strides
     uint32_t mask4[4];                         // hashed level with 2^k rows: (rows - 1) * 4, else 0
 };
 
@@ -68,9 +68,13 @@ __device__ __forceinline__ void rf_setup_levels(const rf_params& P, int g, rf_la
             } else dense = false;
         }
         if (stride > size) dense = false;
-        if (rs + 1 > 1024u) dense = false;     // keeps the 24-bit multiplies of the dense path exact; such a level is hashed anyway
+        // `dense` is the reference's decision, taken from a 32-bit stride product: from a side of 2^16 on the product wraps to a small number, the
+        // reference then does NOT hash the level and indexes it with the wrapped strides modulo its size (gridencoder.hip ge_index, the oracle).  Only a
+        // level whose strides are exact has x + y s1 + z s2 < size and fits the 24-bit multiplies of the dense path; a wrapped one is marked by bit 0 of
+        // s1b (byte strides are multiples of 4; s1, s2 <= size < 2^30) and takes the generic class, which repeats the reference's arithmetic.
+        const bool exact = dense && rs + 1 <= 1024u && (uint64_t)(rs + 1) * (rs + 1) * (rs + 1) <= (uint64_t)size;
         lv.scale[i] = sc; lv.base4[i] = o0 * 4u; lv.size[i] = size;
-        lv.s1b[i] = dense ? s1 * 4u : 0u; lv.s2b[i] = dense ? s2 * 4u : 0u;
+        lv.s1b[i] = dense ? (s1 * 4u) | (exact ? 0u : 1u) : 0u; lv.s2b[i] = dense ? s2 * 4u : 0u;
         lv.mask4[i] = (!dense && (size & (size - 1)) == 0) ? (size - 1) * 4u : 0u;
     }
 }
@@ -82,8 +86,8 @@ __device__ __forceinline__ rf_iter_class rf_classify(const rf_lane_levels& lv) {
     rf_iter_class c = {0u, 0u, 0u};
     #pragma unroll
     for (int i = 0; i < 4; i++) {
-        const unsigned long long bd = __ballot(lv.s1b[i] != 0u), bh = __ballot(lv.mask4[i] != 0u);
-        if (bd == ~0ull) c.dense |= 1u << i;                       // every lane: dense level
+        const unsigned long long bd = __ballot(lv.s1b[i] != 0u && (lv.s1b[i] & 1u) == 0u), bh = __ballot(lv.mask4[i] != 0u);
+        if (bd == ~0ull) c.dense |= 1u << i;                       // every lane: dense level (exact strides)
         else if (bh == ~0ull) c.hashed |= 1u << i;                 // every lane: hashed level with 2^k rows
         else if ((bd | bh) == ~0ull) c.select |= 1u << i;          // a mix of those two
     }                                                              // otherwise (a hashed level whose size is not 2^k): generic
@@ -174,14 +178,16 @@ __device__ __forceinline__ void rf_gather_pair(const rf_params& P, const rf_lane
             } else {
                 // generic: any mix, including a hashed level whose row count is not a power of two (index % size);
                 // branch-free like the rest, so that the choice of class stays the only (wave-uniform) control flow
+                // ... and a level the reference indexes with WRAPPED 32-bit strides (rf_setup_levels): the sum mod 2^32, then modulo the level's size like
+                // a hashed index (an exact dense index is below the size: the modulo leaves it alone)
                 const bool dense = lv.s1b[i] != 0u;
                 const uint32_t s1 = lv.s1b[i] >> 2, s2 = lv.s2b[i] >> 2;
                 const uint32_t hy = gy * P1, hz = gz * P2;
                 #pragma unroll
                 for (int c = 0; c < 8; c++) {
                     const uint32_t id = (gx + (c & 1)) + (gy * s1 + ((c & 2) ? s1 : 0u)) + (gz * s2 + ((c & 4) ? s2 : 0u));
-                    const uint32_t ih = ((gx + (c & 1)) ^ (hy + ((c & 2) ? P1 : 0u)) ^ (hz + ((c & 4) ? P2 : 0u))) % lv.size[i];
-                    off[c] = (dense ? id : ih) * 4u + lv.base4[i];
+                    const uint32_t ih = (gx + (c & 1)) ^ (hy + ((c & 2) ? P1 : 0u)) ^ (hz + ((c & 4) ? P2 : 0u));
+                    off[c] = ((dense ? id : ih) % lv.size[i]) * 4u + lv.base4[i];
                 }
             }
             {
