@@ -480,8 +480,8 @@ typedef struct {
     float density_scale;         /* NeRFRenderer.density_scale (nerf/renderer.py:208) */
 } ngp_nav_field_t;
 
-/* Transposed copies of sigma_w0 and color_w1 the kernels read (ngp_nav_field_workspace() bytes, caller-owned, device); call again
- * whenever those weights change.  Every entry point below takes the same `prepared` pointer. */
+/* Transposed copies of sigma_w0 and color_w1 the kernels read (ngp_nav_field_workspace() bytes, caller-owned, device); call again whenever those weights
+ * change.  Validates the WHOLE field as the entry points below do (same `prepared`), their refusal of a level indexed with wrapped 32-bit strides included. */
 size_t ngp_nav_field_workspace(void);
 int ngp_nav_field_prepare(const ngp_nav_field_t* field_host, void* workspace, size_t workspace_bytes, void* stream);
 

@@ -152,17 +152,11 @@ __device__ __forceinline__ void ft_enc_store(uint32_t* __restrict__ enc, uint32_
 __global__ __launch_bounds__(256) void k_ft_encode_levels(rf_params P, const float* __restrict__ xyzs, uint32_t M, uint32_t Mp, uint32_t* __restrict__ enc) {
     constexpr int SPT = FT_ENC_SPT;
     const uint32_t level = blockIdx.y;
-    // the level's constants (wave-uniform): get_grid_index (gridencoder.cu:54-72) -- strides grow while they fit; a level whose last stride does not fit is hashed
+    // the level's constants (wave-uniform): ngp_classify_level (ngp_device.h)
     const uint32_t o0 = (uint32_t)P.offsets[level], size = (uint32_t)P.offsets[level + 1] - o0;
     const float scale = P.scale[level];
-    const uint32_t side = P.resolution[level] + 1u;
-    uint32_t stride = 1, s1 = 0, s2 = 0;
-    #pragma unroll
-    for (int d = 0; d < 3; d++)
-        if (stride <= size) { if (d == 1) s1 = stride; if (d == 2) s2 = stride; stride *= side; }
-    const bool dense = stride <= size;                                     // the reference's decision, from its 32-bit stride product
-    // from a side of 2^16 on that product wraps: the reference still indexes the level, with the wrapped strides, modulo its size (rf_setup_levels)
-    const bool wrapped = dense && (uint64_t)side * side * side > (uint64_t)size;
+    const ngp_level_index ix = ngp_classify_level(size, P.resolution[level] + 1u);
+    const bool dense = ix.dense, wrapped = dense && !ix.exact;
     const bool pow2 = (size & (size - 1u)) == 0u;
     const uint32_t* tab = P.table + o0;
 
@@ -186,15 +180,15 @@ __global__ __launch_bounds__(256) void k_ft_encode_levels(rf_params P, const flo
             f[q][d] = p - fl;
         }
         if (dense) {                                                       // x + y s1 + z s2 < size by construction, unless the strides wrapped
-            const uint32_t i0 = pg[0] + pg[1] * s1 + pg[2] * s2;
+            const uint32_t i0 = pg[0] + pg[1] * ix.s1 + pg[2] * ix.s2;
             #pragma unroll
             for (int c = 0; c < 8; c++) {
-                uint32_t idx = i0 + (c & 1) + ((c & 2) ? s1 : 0u) + ((c & 4) ? s2 : 0u);
+                uint32_t idx = i0 + (c & 1) + ((c & 2) ? ix.s1 : 0u) + ((c & 4) ? ix.s2 : 0u);
                 if (wrapped) idx = pow2 ? (idx & (size - 1u)) : (idx % size);      // (wave-uniform)
                 raw[q][c] = tab[idx];
             }
         } else {
-            constexpr uint32_t P1 = 2654435761u, P2 = 805459861u;          // fast_hash (gridencoder.cu:35-51)
+            constexpr uint32_t P1 = NGP_HASH_P1, P2 = NGP_HASH_P2;
             const uint32_t hy[2] = {pg[1] * P1, (pg[1] + 1u) * P1}, hz[2] = {pg[2] * P2, (pg[2] + 1u) * P2};
             #pragma unroll
             for (int c = 0; c < 8; c++) {
@@ -223,7 +217,7 @@ template <bool FIXED>
 __device__ __forceinline__ void ft_train_forward_loop(const rf_params& P, const rf_iter_class cls_rt, const rf_lane_levels& lv, const ngp_h8* __restrict__ lds_w,
                                                       const float* __restrict__ xyzs, const float* __restrict__ dirs, uint32_t M,
                                                       float* __restrict__ sigmas, float* __restrict__ rgbs, uint32_t* __restrict__ enc, bool encoded) {
-    const rf_iter_class cls = FIXED ? rf_iter_class{1u, 12u, 2u} : cls_rt;
+    const rf_iter_class cls = FIXED ? RF_DEFAULT_CLASSES : cls_rt;
     const int lane = threadIdx.x & 63, g = lane >> 4, s = lane & 15;
     const uint32_t wave = (blockIdx.x * RF_BLOCK + threadIdx.x) >> 6, nwaves = gridDim.x * (RF_BLOCK / 64);
     const uint32_t npairs = (M + 31) >> 5, Mp = npairs << 5;
@@ -300,7 +294,7 @@ __global__ __launch_bounds__(RF_BLOCK, FT_FWD_WG_PER_CU) void k_field_train_forw
     rf_setup_levels(P, g, lv);
     __syncthreads();
     const rf_iter_class cls = rf_classify(lv);
-    if (cls.dense == 1u && cls.select == 2u && cls.hashed == 12u) ft_train_forward_loop<true>(P, cls, lv, lds_w, xyzs, dirs, M, sigmas, rgbs, enc, encoded);
+    if (rf_is_default(cls)) ft_train_forward_loop<true>(P, cls, lv, lds_w, xyzs, dirs, M, sigmas, rgbs, enc, encoded);
     else ft_train_forward_loop<false>(P, cls, lv, lds_w, xyzs, dirs, M, sigmas, rgbs, enc, encoded);
 }
 

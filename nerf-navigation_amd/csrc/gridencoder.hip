@@ -41,7 +41,7 @@ template <> struct ge_num<_Float16> {
 
 template <typename T, uint32_t C> struct alignas(sizeof(T) * C) ge_vec { T v[C]; };
 
-static __device__ __constant__ const uint32_t GE_PRIMES[7] = {1u, 2654435761u, 805459861u, 3674653429u, 2097192037u, 1434869437u, 2165219737u};
+static __device__ __constant__ const uint32_t GE_PRIMES[7] = {1u, NGP_HASH_P1, NGP_HASH_P2, 3674653429u, 2097192037u, 1434869437u, 2165219737u};
 
 template <uint32_t D>
 __device__ __forceinline__ uint32_t ge_index(uint32_t gridtype, bool align_corners, uint32_t hashmap_size,
@@ -807,16 +807,9 @@ __global__ __launch_bounds__(1024) void k_gs_bin(const _Float16* __restrict__ gr
     for (int k = 0; k < 4; k++) take[k] = (lane - (1 << k) >= start) ? 1.0f : 0.0f;        // row_shr:2^k (a source outside the row reads 0)
     take[4] = (start < (lane & ~15)) ? 1.0f : 0.0f;                                        // the run reaches into the row below
     take[5] = (lane >= 32 && start < 32) ? 1.0f : 0.0f;                                    // ... and into the lower half of the wave
-    // how this level is indexed (uniform over the workgroup): the strides of get_grid_index, and whether they all fit (dense) or the level is hashed
-    const uint32_t side = align_corners ? resolution : resolution + 1u;
-    const uint32_t s1 = side, s2 = side * side;
-    const bool idx_dense = (uint64_t)side * side * side <= (uint64_t)level_rows;           // every stride fits: x + y s1 + z s2 < rows, no modulo
-    // whether get_grid_index hashes is decided by ITS stride, a 32-bit product: from a side of 2^16 on (per_level_scale 2 from resolution 16: levels 12-15) it
-    // wraps to a small number, the reference then does not hash the level, and neither may this kernel (ge_index below repeats the wrapped strides)
-    uint32_t stride = 1;
-    #pragma unroll
-    for (uint32_t d = 0; d < D; d++) if (stride <= level_rows) stride *= side;
-    const bool idx_pow2 = !idx_dense && gridtype == 0 && stride > level_rows && (level_rows & (level_rows - 1u)) == 0;   // hashed, 2^k rows: the modulo is a mask
+    // how this level is indexed (uniform over the workgroup): ngp_classify_level (ngp_device.h); a wrapped level goes to ge_index
+    const ngp_level_index ix = ngp_classify_level(level_rows, align_corners ? resolution : resolution + 1u);
+    const bool idx_pow2 = !ix.dense && gridtype == 0 && (level_rows & (level_rows - 1u)) == 0;   // hashed, 2^k rows: the modulo is a mask
     __syncthreads();                                   // s_hist is zero
 
     uint32_t e_val[8], e_key[8], e_rank[8];
@@ -850,8 +843,8 @@ __global__ __launch_bounds__(1024) void k_gs_bin(const _Float16* __restrict__ gr
         // run-time divisor is ~20 VALU instructions, eight times per lane, in a kernel that is VALU-bound (profiles/r15_train): a level is either
         // dense (its last stride fits: the index is below the row count by construction) or hashed with 2^k rows (mask); wave-uniform choice
         uint32_t row;
-        if (idx_dense) row = pl[0] + pl[1] * s1 + pl[2] * s2;
-        else if (idx_pow2) row = (pl[0] ^ (pl[1] * 2654435761u) ^ (pl[2] * 805459861u)) & (level_rows - 1u);
+        if (ix.exact) row = pl[0] + pl[1] * ix.s1 + pl[2] * ix.s2;
+        else if (idx_pow2) row = (pl[0] ^ (pl[1] * NGP_HASH_P1) ^ (pl[2] * NGP_HASH_P2)) & (level_rows - 1u);
         else row = ge_index<D>(gridtype, align_corners, level_rows, resolution, pl);
         h2 hv;
         hv.x = ngp_f2h(v0);

@@ -69,7 +69,7 @@ struct nav_params {
 
 __device__ __forceinline__ uint32_t nv_row(const nav_params& P, int l, uint32_t x, uint32_t y, uint32_t z) {
     if (P.lv.s1[l]) return P.lv.base[l] + x + y * P.lv.s1[l] + z * P.lv.s2[l];                    // dense level: always < size
-    const uint32_t h = x ^ (y * 2654435761u) ^ (z * 805459861u);                                   // fast_hash (gridencoder.cu:35-51)
+    const uint32_t h = x ^ (y * NGP_HASH_P1) ^ (z * NGP_HASH_P2);                                  // fast_hash (gridencoder.cu:35-51)
     return P.lv.base[l] + (P.lv.mask[l] ? (h & P.lv.mask[l]) : (h % P.lv.size[l]));
 }
 
@@ -720,10 +720,41 @@ static nav_prep_ws nav_prep_layout(void* base) {
 }
 extern "C" size_t ngp_nav_field_workspace(void) { return nav_prep_layout(nullptr).total; }
 
+static int nav_fill(const char* who, const ngp_nav_field_t* f, const void* prepared, nav_params& P) {
+    NGP_REQUIRE(f && f->embeddings && f->offsets_host && f->sigma_w0 && f->sigma_w1 && f->color_w0 && f->color_w1 && f->color_w2 && prepared,
+                "%s: null field pointer", who);
+    NGP_REQUIRE(f->L == NV_L && f->bound > 0.0f, "%s: the fused nav queries are built for the default field (16 levels x 2 features, 32-64-16 | 31-64-64-3)", who);
+    P.table = (const float2*)f->embeddings;
+    const nav_prep_ws prep = nav_prep_layout(const_cast<void*>(prepared));
+    P.w1t = (nv_wptr)(uintptr_t)prep.w1t; P.w2t = (nv_wptr)(uintptr_t)prep.w2t;
+    P.v0t = (nv_wptr)(uintptr_t)prep.v0t; P.v1t = (nv_wptr)(uintptr_t)prep.v1t; P.v2t = (nv_wptr)(uintptr_t)prep.v2t;
+    P.w2 = (nv_wptr)(uintptr_t)f->sigma_w1; P.v0 = (nv_wptr)(uintptr_t)f->color_w0;
+    P.v1 = (nv_wptr)(uintptr_t)f->color_w1; P.v2 = (nv_wptr)(uintptr_t)f->color_w2;
+    for (int l = 0; l < NV_L; l++) {
+        const float sc = ngp_level_scale((uint32_t)l, f->S, f->H);
+        const uint32_t side = ngp_level_resolution(sc) + 1u;
+        const uint32_t o0 = (uint32_t)f->offsets_host[l], size = (uint32_t)f->offsets_host[l + 1] - o0;
+        NGP_REQUIRE(size > 0, "%s: empty level %d", who, l);
+        const ngp_level_index ix = ngp_classify_level(size, side);          // (ngp_device.h)
+        // nv_row adds a dense level's strides without a modulo, which is only right for exact strides
+        NGP_REQUIRE(!ix.dense || ix.exact, "%s: level %d (side %u, %u rows) is indexed with wrapped 32-bit strides, which the fused nav kernels do not implement; "
+                    "query this field through NavQueries' op chain instead", who, l, side, size);
+        P.lv.scale[l] = sc; P.lv.base[l] = o0; P.lv.size[l] = size;
+        P.lv.mask[l] = (size & (size - 1)) == 0 ? size - 1 : 0u;
+        P.lv.s1[l] = ix.dense ? ix.s1 : 0u; P.lv.s2[l] = ix.dense ? ix.s2 : 0u;
+    }
+    sh_fill_norm(P.shn);
+    P.bound = f->bound;
+    P.r2b = 1.0f / (2.0f * f->bound);
+    P.density_scale = f->density_scale;
+    return NGP_OK;
+}
+
 // transposed copies of the five weight matrices into `workspace`; call again whenever the weights change
 extern "C" int ngp_nav_field_prepare(const ngp_nav_field_t* f, void* workspace, size_t workspace_bytes, void* stream) {
-    NGP_REQUIRE(f && f->sigma_w0 && f->color_w1 && workspace && workspace_bytes >= ngp_nav_field_workspace(), "nav_field_prepare: bad argument");
-    NGP_REQUIRE(f->sigma_w1 && f->color_w0 && f->color_w2, "nav_field_prepare: null weight pointer");
+    nav_params P;                                  // the queries' own checks: a field they would refuse is refused when it is set up
+    { const int rc = nav_fill("nav_field_prepare", f, workspace, P); if (rc != NGP_OK) return rc; }
+    NGP_REQUIRE(workspace_bytes >= ngp_nav_field_workspace(), "nav_field_prepare: bad argument");
     const nav_prep_ws w = nav_prep_layout(workspace);
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(k_nav_transpose, dim3(8), dim3(256), 0, st, f->sigma_w0, 64u, 32u, w.w1t);
@@ -742,39 +773,6 @@ static int nav_allow_big_lds() {
                                                    (const void*)k_nav_run_bwd, (const void*)k_nav_density_vj}, 160 * 1024);
     if (rc == NGP_LDS_NO_DEVICE) return ngp_fail(NGP_ELAUNCH, "nav: no current device");
     if (rc != NGP_LDS_OK) return ngp_fail(NGP_ELAUNCH, "nav: cannot raise the dynamic LDS limit");
-    return NGP_OK;
-}
-
-static int nav_fill(const char* who, const ngp_nav_field_t* f, const void* prepared, nav_params& P) {
-    NGP_REQUIRE(f && f->embeddings && f->offsets_host && f->sigma_w0 && f->sigma_w1 && f->color_w0 && f->color_w1 && f->color_w2 && prepared,
-                "%s: null field pointer", who);
-    NGP_REQUIRE(f->L == NV_L && f->bound > 0.0f, "%s: the fused nav queries are built for the default field (16 levels x 2 features, 32-64-16 | 31-64-64-3)", who);
-    P.table = (const float2*)f->embeddings;
-    const nav_prep_ws prep = nav_prep_layout(const_cast<void*>(prepared));
-    P.w1t = (nv_wptr)(uintptr_t)prep.w1t; P.w2t = (nv_wptr)(uintptr_t)prep.w2t;
-    P.v0t = (nv_wptr)(uintptr_t)prep.v0t; P.v1t = (nv_wptr)(uintptr_t)prep.v1t; P.v2t = (nv_wptr)(uintptr_t)prep.v2t;
-    P.w2 = (nv_wptr)(uintptr_t)f->sigma_w1; P.v0 = (nv_wptr)(uintptr_t)f->color_w0;
-    P.v1 = (nv_wptr)(uintptr_t)f->color_w1; P.v2 = (nv_wptr)(uintptr_t)f->color_w2;
-    for (int l = 0; l < NV_L; l++) {
-        const float sc = ngp_level_scale((uint32_t)l, f->S, f->H);
-        const uint32_t rs = ngp_level_resolution(sc);
-        const uint32_t o0 = (uint32_t)f->offsets_host[l], size = (uint32_t)f->offsets_host[l + 1] - o0;
-        uint32_t stride = 1, s1 = 0, s2 = 0;
-        bool dense = true;
-        for (int d = 0; d < 3; d++) {                                    // get_grid_index (gridencoder.cu:54-72)
-            if (stride <= size) { if (d == 1) s1 = stride; if (d == 2) s2 = stride; stride *= rs + 1; }
-            else dense = false;
-        }
-        if (stride > size) dense = false;
-        P.lv.scale[l] = sc; P.lv.base[l] = o0; P.lv.size[l] = size;
-        P.lv.mask[l] = (size & (size - 1)) == 0 ? size - 1 : 0u;
-        P.lv.s1[l] = dense ? s1 : 0u; P.lv.s2[l] = dense ? s2 : 0u;
-        NGP_REQUIRE(size > 0, "%s: empty level %d", who, l);
-    }
-    sh_fill_norm(P.shn);
-    P.bound = f->bound;
-    P.r2b = 1.0f / (2.0f * f->bound);
-    P.density_scale = f->density_scale;
     return NGP_OK;
 }
 

@@ -65,6 +65,32 @@ static inline int ngp_allow_dynamic_lds(std::atomic<unsigned long long>& done, s
 static inline float ngp_level_scale(uint32_t l, float S, uint32_t H) { return exp2f((float)l * S) * (float)H - 1.0f; }
 static inline uint32_t ngp_level_resolution(float scale) { return (uint32_t)ceilf(scale) + 1u; }
 
+// How a level of the D = 3 grid is indexed, host and device: the only statement of the rule besides ge_index (gridencoder.hip, any D).
+static constexpr uint32_t NGP_HASH_P1 = 2654435761u, NGP_HASH_P2 = 805459861u;   // fast_hash (gridencoder.cu:35-51): x ^ y * P1 ^ z * P2 in uint32
+// The reference's get_grid_index (gridencoder.cu:54-72) for a level of `rows` rows and `side` = resolution + 1 points per axis: the strides 1, side,
+// side^2 grow while they fit into `rows`; if the product after the last one does not fit the level is hashed, else dense; either index is taken modulo
+// `rows`.  The decision comes from a 32-BIT product that can wrap to a small number (per_level_scale 2 from resolution 16 has side 2^16 + 1 at level 12;
+// side 1,626 wraps at 2^24 rows): the reference then does NOT hash the level but indexes it with the wrapped strides, and so must every kernel here.
+//   exact    dense, and side^3 <= rows without any wrap: x + y s1 + z s2 < rows, no modulo needed
+//   wrapped  dense by the reference's decision but not exact: (x + y s1 + z s2 mod 2^32) % rows
+//   hashed   !dense: fast_hash % rows (a mask where rows is 2^k)
+// The loop is a macro that declares s1, s2 (the strides it reached, 0 where it stopped before) and dense: rf_setup_levels (ngp_field.h) expands it in place,
+// because the frame kernel compiles to other code throughout, measured 0.2 % slower, when these tokens reach it through an inline function (profiles/HISTORY.md 5.7).
+#define NGP_LEVEL_STRIDES(rows, side, s1, s2, dense) \
+    uint32_t stride = 1, s1 = 0, s2 = 0; \
+    bool dense = true; \
+    _Pragma("unroll") for (int d = 0; d < 3; d++) { \
+        if (stride <= (rows)) { if (d == 1) s1 = stride; if (d == 2) s2 = stride; stride *= (side); } else dense = false; \
+    } \
+    if (stride > (rows)) dense = false;
+// side^3 <= rows in 64 bits; the cube of a side of 2^22 or more would wrap there too
+__host__ __device__ __forceinline__ bool ngp_level_cube_fits(uint32_t rows, uint32_t side) { return side <= (1u << 21) && (uint64_t)side * side * side <= (uint64_t)rows; }
+struct ngp_level_index { uint32_t s1, s2; bool dense, exact; };          // wrapped: dense && !exact
+__host__ __device__ __forceinline__ ngp_level_index ngp_classify_level(uint32_t rows, uint32_t side) {
+    NGP_LEVEL_STRIDES(rows, side, s1, s2, dense)
+    return {s1, s2, dense, dense && ngp_level_cube_fits(rows, side)};
+}
+
 // ---------------------------------------------------------------------------
 // device: scalar helpers
 // ---------------------------------------------------------------------------

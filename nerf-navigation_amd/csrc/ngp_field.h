@@ -56,23 +56,10 @@ __device__ __forceinline__ void rf_setup_levels(const rf_params& P, int g, rf_la
         const int level = 4 * i + g;
         const uint32_t o0 = (uint32_t)P.offsets[level], o1 = (uint32_t)P.offsets[level + 1];
         const uint32_t size = o1 - o0;
-        // reference get_grid_index (gridencoder.cu:54-72): the stride stops growing once it exceeds hashmap_size
-        uint32_t stride = 1, s1 = 0, s2 = 0;
-        bool dense = true;
-        #pragma unroll
-        for (int d = 0; d < 3; d++) {
-            if (stride <= size) {
-                if (d == 1) s1 = stride;
-                if (d == 2) s2 = stride;
-                stride *= (rs + 1);
-            } else dense = false;
-        }
-        if (stride > size) dense = false;
-        // `dense` is the reference's decision, taken from a 32-bit stride product: from a side of 2^16 on the product wraps to a small number, the
-        // reference then does NOT hash the level and indexes it with the wrapped strides modulo its size (gridencoder.hip ge_index, the oracle).  Only a
-        // level whose strides are exact has x + y s1 + z s2 < size and fits the 24-bit multiplies of the dense path; a wrapped one is marked by bit 0 of
-        // s1b (byte strides are multiples of 4; s1, s2 <= size < 2^30) and takes the generic class, which repeats the reference's arithmetic.
-        const bool exact = dense && rs + 1 <= 1024u && (uint64_t)(rs + 1) * (rs + 1) * (rs + 1) <= (uint64_t)size;
+        // the rule of ngp_classify_level (ngp_device.h), expanded in place.  The dense path wants exact strides AND a side within its 24-bit multiplies; any other
+        // dense level is marked by bit 0 of s1b (byte strides are multiples of 4; s1, s2 <= size < 2^30) and takes the generic class, which repeats the reference's arithmetic.
+        NGP_LEVEL_STRIDES(size, rs + 1, s1, s2, dense)
+        const bool exact = dense && rs + 1 <= 1024u && ngp_level_cube_fits(size, rs + 1);
         lv.scale[i] = sc; lv.base4[i] = o0 * 4u; lv.size[i] = size;
         lv.s1b[i] = dense ? (s1 * 4u) | (exact ? 0u : 1u) : 0u; lv.s2b[i] = dense ? s2 * 4u : 0u;
         lv.mask4[i] = (!dense && (size & (size - 1)) == 0) ? (size - 1) * 4u : 0u;
@@ -81,6 +68,8 @@ __device__ __forceinline__ void rf_setup_levels(const rf_params& P, int g, rf_la
 
 // Which kind of code each iteration needs, decided once per kernel by the whole wave (bit i = iteration i).
 struct rf_iter_class { uint32_t dense, hashed, select; };
+static constexpr rf_iter_class RF_DEFAULT_CLASSES = rf_iter_class{1u, 12u, 2u};    // the reference's 16-level grid (rf_lane_levels): loops are also compiled with these as constants
+__device__ __forceinline__ bool rf_is_default(const rf_iter_class& cls) { return cls.dense == 1u && cls.select == 2u && cls.hashed == 12u; }
 
 __device__ __forceinline__ rf_iter_class rf_classify(const rf_lane_levels& lv) {   // call with all 64 lanes active
     rf_iter_class c = {0u, 0u, 0u};
@@ -130,7 +119,7 @@ __device__ __forceinline__ void rf_normalise(const rf_params& P, float wx, float
 template <int H>
 __device__ __forceinline__ void rf_gather_pair(const rf_params& P, const rf_lane_levels& lv, const rf_iter_class cls,
                                                float x0, float x1, float x2, rf_pair& o) {
-    constexpr uint32_t P1 = 2654435761u, P2 = 805459861u;              // fast_hash primes (gridencoder.cu:35-51)
+    constexpr uint32_t P1 = NGP_HASH_P1, P2 = NGP_HASH_P2;
     // positions of the two levels at once: packed binary32 multiply and add (same roundings as the scalar operations)
     typedef float f2 __attribute__((ext_vector_type(2)));
     const f2 sc2 = {lv.scale[2 * H], lv.scale[2 * H + 1]};
@@ -178,8 +167,7 @@ __device__ __forceinline__ void rf_gather_pair(const rf_params& P, const rf_lane
             } else {
                 // generic: any mix, including a hashed level whose row count is not a power of two (index % size);
                 // branch-free like the rest, so that the choice of class stays the only (wave-uniform) control flow
-                // ... and a level the reference indexes with WRAPPED 32-bit strides (rf_setup_levels): the sum mod 2^32, then modulo the level's size like
-                // a hashed index (an exact dense index is below the size: the modulo leaves it alone)
+                // ... and a wrapped level (ngp_classify_level): the sum mod 2^32, then % size like a hashed index (which leaves an exact dense index alone)
                 const bool dense = lv.s1b[i] != 0u;
                 const uint32_t s1 = lv.s1b[i] >> 2, s2 = lv.s2b[i] >> 2;
                 const uint32_t hy = gy * P1, hz = gz * P2;

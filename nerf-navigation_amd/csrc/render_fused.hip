@@ -269,7 +269,7 @@ template <bool FIXED>
 __device__ __forceinline__ void rf_points_loop(const rf_params& P, const rf_iter_class cls_rt, const rf_lane_levels& lv, const ngp_h8* __restrict__ lds_w,
                                                const float* __restrict__ xyzs, const float* __restrict__ dirs, uint32_t M,
                                                float* __restrict__ sigmas, void* __restrict__ rgbs_v, bool rgb_half) {
-    const rf_iter_class cls = FIXED ? rf_iter_class{1u, 12u, 2u} : cls_rt;
+    const rf_iter_class cls = FIXED ? RF_DEFAULT_CLASSES : cls_rt;
     const int lane = threadIdx.x & 63, g = lane >> 4, s = lane & 15;
     const uint32_t wave = (blockIdx.x * RF_BLOCK + threadIdx.x) >> 6, nwaves = gridDim.x * (RF_BLOCK / 64);
     const uint32_t npairs = (M + 31) >> 5;
@@ -322,7 +322,7 @@ __global__ __launch_bounds__(RF_BLOCK, RF_FIELD_WG_PER_CU) void k_field_forward_
     rf_setup_levels(P, g, lv);
     __syncthreads();
     const rf_iter_class cls = rf_classify(lv);
-    if (cls.dense == 1u && cls.select == 2u && cls.hashed == 12u) rf_points_loop<true>(P, cls, lv, lds_w, xyzs, dirs, M, sigmas, rgbs, rgb_half);
+    if (rf_is_default(cls)) rf_points_loop<true>(P, cls, lv, lds_w, xyzs, dirs, M, sigmas, rgbs, rgb_half);
     else rf_points_loop<false>(P, cls, lv, lds_w, xyzs, dirs, M, sigmas, rgbs, rgb_half);
 }
 
@@ -377,7 +377,7 @@ template <bool FIXED>
 __device__ __forceinline__ void rv_frame_loop(const rf_params& P, const rf_frame& F, const rf_iter_class cls_rt,
                                               const ngp_h8* __restrict__ lds_w, _Float16* lds_sh, const rf_lane_levels* lds_lv,
                                               float4* lds_smp, const uint32_t* lds_coarse, const float* lds_occ) {
-    const rf_iter_class cls = FIXED ? rf_iter_class{1u, 12u, 2u} : cls_rt;
+    const rf_iter_class cls = FIXED ? RF_DEFAULT_CLASSES : cls_rt;
     const int lane = threadIdx.x & 63, g = lane >> 4, s = lane & 15, wave = threadIdx.x >> 6;
     const int wave_s = __builtin_amdgcn_readfirstlane(wave);          // the same, known to be uniform
 
@@ -749,7 +749,7 @@ __global__ __launch_bounds__(RV_BLOCK, RV_WAVES_PER_SIMD) void k_render_frame_mu
     }
     __syncthreads();
     const rf_iter_class cls = rf_classify(lds_lv[g]);
-    if (cls.dense == 1u && cls.select == 2u && cls.hashed == 12u)
+    if (rf_is_default(cls))
         rv_frame_loop<true>(P, F, cls, lds_w, lds_sh, lds_lv, lds_smp, lds_coarse, lds_occ);
     else
         rv_frame_loop<false>(P, F, cls, lds_w, lds_sh, lds_lv, lds_smp, lds_coarse, lds_occ);

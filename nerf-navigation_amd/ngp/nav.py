@@ -194,7 +194,8 @@ class _NativeField:
         return [f.encoder.embeddings, f.sigma_net[0].weight, f.sigma_net[1].weight, f.color_net[0].weight, f.color_net[1].weight, f.color_net[2].weight]
 
     def struct(self):
-        """(ngp_nav_field_t, prepared-weights tensor); the transposes are redone only when a parameter changed"""
+        """(ngp_nav_field_t, prepared-weights tensor); the transposes are redone only when a parameter changed.  ngp_nav_field_prepare judges the
+        field as the queries do: a grid with a level the reference indexes by wrapped 32-bit strides (bound 256) raises here, naming the level."""
         _hip, ct = self._hip, self._ct
         ps = self._params()
         key = tuple((p.data_ptr(), p._version, str(p.device)) for p in ps) + (float(self.field.bound), float(self.renderer.density_scale), getattr(self.field, "_param_epoch", 0))

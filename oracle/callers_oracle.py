@@ -49,7 +49,7 @@ def _grid_index(loc, hashmap_size, resolution, gridtype, align_corners):
     d = 0
     while d < len(loc) and stride <= hashmap_size:
         index = (index + loc[d] * stride) & MASK32
-        stride *= step
+        stride = (stride * step) & MASK32                          # a uint32 product: it wraps, and the decision below is taken from the wrapped value
         d += 1
     if gridtype == 0 and stride > hashmap_size:
         index = torch.zeros_like(loc[0])
