@@ -454,6 +454,20 @@ int ngp_render_set_occupied_box(int enabled);
  * coarse occupancy map and hands out each image band's tiles by decreasing cost, so that the frame ends on cheap tiles.  0 = row-major tiles.
  * Validation and A/B only: results are identical either way; returns the previous setting. */
 int ngp_render_set_tile_order(int enabled);
+/* A/B switch, process-wide, default 0: with the tile order above, 1 = a wave of ngp_render_frame draws its next tile from the band -- of its XCD's
+ * four -- whose next tile is estimated most expensive, so that the XCD ends on the cheapest tiles of its whole share; 0 = the bands one after the other,
+ * top to bottom.  Without a tile order both are the same walk.  Off by default: it helps views from above and below the scene and costs on others
+ * (profiles/HISTORY.md 5.8).  Results are identical either way; returns the previous setting. */
+int ngp_render_set_band_merge(int enabled);
+/* The pick's hysteresis, process-wide, default 4: a wave leaves the band of its previous tile only for a tile estimated more than h times as
+ * expensive (1 <= h <= 64, rounded to 1/256; 1 = always the most expensive).  Returns the previous h. */
+float ngp_render_set_band_hysteresis(float h);
+/* The pick itself, evaluated on the host by the function the kernel calls (csrc/ngp_band_pick.h), for tests: heads [32] = rays handed out per band of a
+ * frame of n_rays rays, perm / cost = the tile order and the estimates in host memory (both null: none), xcd 0..7, dry_mask = bands the wave has found
+ * dry, last_band = the band of its previous tile or -1.  *band_out = the band to draw from, -1 when none has tiles left; *dry_mask_out (optional) =
+ * dry_mask with the bands this look found dry or empty. */
+int ngp_render_band_pick_host(const uint32_t* heads, uint32_t n_rays, const uint32_t* perm, const uint32_t* cost, uint32_t xcd, uint32_t dry_mask,
+                              int last_band, float h, int* band_out, uint32_t* dry_mask_out);
 int ngp_render_frame(const ngp_field_t* field_host, const float* rays_o, const float* rays_d, uint32_t N,
                      uint32_t image_width, const float* aabb, float min_near, const uint8_t* bitfield, uint32_t C, uint32_t Hgrid,
                      float dt_gamma, uint32_t max_steps, const float* bg_color3_host,

@@ -28,6 +28,7 @@
 #include "ngp_field.h"
 #include "ngp_march.h"
 #include "ngp_camera.h"
+#include "ngp_band_pick.h"
 
 __global__ void k_field_forward_lds(rf_params P, const float* __restrict__ xyzs, const float* __restrict__ dirs, uint32_t M,
                                     float* __restrict__ sigmas, void* __restrict__ rgbs, bool rgb_half);
@@ -109,7 +110,8 @@ static_assert(RV_S >= 2, "RV_S must be at least 2: the one-sample-per-round fram
 #define RV_BLOCKS_PER_CU 1             // the sample slots (96 KiB at 512 x 12) only fit beside ONE copy of the weights per CU
 #endif
 // (software pipelining across tiles, a global most-expensive-first tile order and CU-local tile chunks were measured slower: profiles/HISTORY.md 1, 3.2;
-//  most-expensive-first WITHIN each band, from a per-frame estimate, is kept: k_tile_cost, profiles/HISTORY.md 5.1)
+//  most-expensive-first WITHIN each band, from a per-frame estimate, is kept: k_tile_cost, profiles/HISTORY.md 5.1; a wave finds its next band in
+//  one look at all 32 queues, and may merge its XCD's bands by those estimates: ngp_band_pick.h, 5.8)
 static constexpr uint32_t RV_BLOCK = RV_BLOCK_THREADS;
 static constexpr int RV_WAVES_PER_SIMD = (RV_BLOCK_THREADS / 256) * RV_BLOCKS_PER_CU;
 static constexpr int RV_WAVES = RV_BLOCK / 64;
@@ -138,6 +140,8 @@ struct rf_frame {
     const uint32_t* occ_ext;         // the extent of the occupied blocks (k_build_coarse), or null: a ray marches no further than where it leaves that box
     float occ_unit, occ_top;         // world size of one unit of that lattice, and the half-width of the outermost cascade (its origin is -occ_top)
     const uint32_t* tile_perm;       // tile_w != 0: queue position -> 8x8 tile, each band's tiles by decreasing estimated cost (k_tile_sort), or null: row-major
+    const uint32_t* tile_cost;       // with tile_perm: each tile's estimate (k_tile_cost), by which a wave picks among the bands; null: the bands one after the other
+    uint32_t band_h_q8;              // the pick's hysteresis in 1/256 (ngp_band_pick.h)
 };
 
 // coarse[level][m] = any fine bit set in Morton block m (64 bits = 8 bytes of the bitfield)
@@ -402,7 +406,9 @@ __device__ __forceinline__ void rv_frame_loop(const rf_params& P, const rf_frame
     float t = 0, last_t = 0, near = 0, far = 0;
     float ws = 0, dacc = 0, cr = 0, cg = 0, cb = 0, tcomp = 0;
     bool exhausted = false;
-    uint32_t rv_q = blockIdx.x & 7u, rv_q_seen = 0;        // blockIdx % 8 labels the workgroups that share an XCD
+    uint32_t rv_dry = 0;                               // bands this wave has seen run dry (or empty): never drawn from again
+    uint32_t rv_home = (blockIdx.x & 7u) << 8;         // bits 8..10: blockIdx % 8 labels the workgroups that share an XCD; bits 0..7: 1 + the band of this
+                                                       // wave's previous tile, 0 = none yet (ngp_band_pick.h: hysteresis)
     rv_block_cache bc;                                 // bitfield word of the block the ray last tested (block ids are global: stays valid across rays)
     uint32_t n_samples_local = 0, n_tiles = 0, n_capped_local = 0, n_hit_local = 0;
 #ifdef RV_COUNTERS
@@ -428,17 +434,37 @@ __device__ __forceinline__ void rv_frame_loop(const rf_params& P, const rf_frame
             const unsigned long long need = __ballot(!active);
             if (need && (uint32_t)__popcll(need) >= RV_REFILL_MIN) {
                 const uint32_t cnt = (uint32_t)__popcll(need);
-                uint32_t base = 0;
                 // Queue q holds the rays of image band q (tiles [T q / RV_BANDS, T (q + 1) / RV_BANDS) of 64 rays): the workgroups of one XCD
-                // work on the same band, so that the table lines neighbouring rays share are fetched into ONE L2 and
-                // not into eight.  A wave that finds its queue empty moves on to its XCD's next band, then to the other XCDs'.
-                const uint32_t n_tiles64 = (F.N + 63u) >> 6;
-                const uint32_t q_lo = (uint32_t)(((unsigned long long)n_tiles64 * rv_q) / RV_BANDS) << 6;
-                uint32_t q_hi = (uint32_t)(((unsigned long long)n_tiles64 * (rv_q + 1u)) / RV_BANDS) << 6;
-                q_hi = q_hi < F.N ? q_hi : F.N;
-                if (lane == 0) base = atomicAdd(F.queue + 32 + rv_q, cnt);
-                base = __shfl(base, 0, 64) + q_lo;
-                if (!active) {
+                // work on the same bands (x, x + 8, x + 16, x + 24), so that the table lines neighbouring rays share are fetched into ONE L2 and
+                // not into eight; when its own are dry an XCD goes on with the next XCD's.
+                // The wave picks its band itself (ngp_band_pick.h): lane b looks at band b -- its head, and with a tile order the estimate of its next
+                // tile -- and the largest key wins: own bands first, then the most expensive next tile, then the order above.  The looks are hints
+                // (a head may be stale, but heads only grow); the atomicAdd decides, and a band is never drawn from again once a draw or a look found it dry.
+                // (the lane's band and the pick's uniform inputs are formed here, opaquely: otherwise what depends on them alone -- the lane's range, the
+                //  rank of its band -- is hoisted out of the frame loop and lives in registers through the march and the field evaluation, which have
+                //  none to spare)
+                uint32_t band = threadIdx.x & 63u, rv_z = 0u;
+                asm volatile("" : "+v"(band), "+s"(rv_z));
+                const uint32_t xcd = rv_home >> 8, n_rays = F.N + rv_z;
+                unsigned long long key = 0ull;
+                bool peek_dry = false;
+                if (band < RV_BANDS && !((rv_dry >> band) & 1u)) {
+                    const uint32_t head = __hip_atomic_load(F.queue + 32 + band, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    key = ngp_band_look(band, xcd, RV_BANDS, n_rays, head, rv_dry, (int)(rv_home & 255u) - 1, F.band_h_q8 + rv_z, F.tile_perm, F.tile_cost, &peek_dry);
+                }
+                rv_dry |= (uint32_t)__ballot(peek_dry);
+                #pragma unroll
+                for (int off = 16; off > 0; off >>= 1) key = ngp_band_better(key, __shfl_xor(key, off, 64));   // lanes 0..31 hold the keys
+                // (a key names its band by its low 5 bits and by not being zero: that much goes through readfirstlane)
+                const int pick = ngp_band_of_key((unsigned long long)__builtin_amdgcn_readfirstlane((int)((key ? 32u : 0u) | (uint32_t)(key & 31u))), xcd, RV_BANDS);
+                uint32_t base = 0, q_lo = 0, q_hi = 0;
+                if (pick >= 0) {
+                    ngp_band_range(n_rays, (uint32_t)pick, RV_BANDS, q_lo, q_hi);
+                    if (lane == 0) base = atomicAdd(F.queue + 32 + pick, cnt);
+                    base = __shfl(base, 0, 64) + q_lo;
+                    rv_home = (rv_home & ~255u) | (uint32_t)(pick + 1);
+                }
+                if (pick >= 0 && !active) {
                     const uint32_t idx = base + (uint32_t)__popcll(need & ((1ull << lane) - 1ull));
                     if (idx < q_hi) {
                         // the band's tiles are handed out by decreasing estimated cost (tile_perm stays within the band), so that its cheapest tiles end the frame
@@ -465,14 +491,11 @@ __device__ __forceinline__ void rv_frame_loop(const rf_params& P, const rf_frame
                         active = true;
                     }
                 }
-                if (base + cnt >= q_hi) {                  // this queue has run dry: move on, until all eight have been seen
-                    // XCD x owns bands x, x + 8, x + 16, ...: thin bands spread over the whole image, so that every XCD gets a fair sample of cheap and
-                    // expensive rows; when its own are done it goes on with the next XCD's (top to bottom: ordering the bands by their estimated cost
-                    // instead was measured slower, profiles/HISTORY.md 5.1)
-                    rv_q += 8u;
-                    if (rv_q >= RV_BANDS) rv_q = (rv_q + 1u) & 7u;
-                    if (++rv_q_seen == RV_BANDS) exhausted = true;
-                }
+                // XCD x owns bands x, x + 8, x + 16, ...: thin bands spread over the whole image, so that every XCD gets a fair sample of cheap and
+                // expensive rows.  Without estimates the pick walks them top to bottom, then the next XCD's (ranking whole bands by their estimated
+                // totals was measured slower, profiles/HISTORY.md 5.1; merging them tile by tile: 5.8)
+                if (pick >= 0 && base + cnt >= q_hi) rv_dry |= 1u << pick;       // this queue has run dry under this wave
+                exhausted = rv_dry == (RV_BANDS >= 32u ? 0xFFFFFFFFu : (1u << (RV_BANDS & 31u)) - 1u);   // no pick: every band was already marked
             }
         }
         if (__ballot(active) == 0ull) {
@@ -851,6 +874,32 @@ extern "C" int ngp_render_set_block_skip(int enabled) { return rv_block_skip_ena
 static std::atomic<int> rv_tile_order_enabled{1};
 // validation switch: 0 = every band's tiles in row-major order; results are identical either way
 extern "C" int ngp_render_set_tile_order(int enabled) { return rv_tile_order_enabled.exchange(enabled ? 1 : 0, std::memory_order_relaxed); }
+static std::atomic<int> rv_band_merge_enabled{0};
+// A/B switch: 1 = with a tile order, a wave picks the band whose next tile is estimated most expensive among its XCD's bands (ngp_band_pick.h);
+// 0 = the bands one after the other.  Results are identical either way.  Off by default: on bench's orbit the merge gained 0.4-0.5 % over the bands
+// one after the other, inside the run-to-run spread, and the fitted model's frame lost 2.2 % (profiles/HISTORY.md 5.8)
+extern "C" int ngp_render_set_band_merge(int enabled) { return rv_band_merge_enabled.exchange(enabled ? 1 : 0, std::memory_order_relaxed); }
+static std::atomic<uint32_t> rv_band_h_q8{4u * NGP_BAND_H_ONE};          // the best of h = 1, 2, 4, 8 on bench's orbit
+static uint32_t rv_band_h_to_q8(float h) { return !(h > 1.0f) ? NGP_BAND_H_ONE : h >= 64.0f ? NGP_BAND_H_MAX : (uint32_t)(h * 256.0f + 0.5f); }
+// the pick's hysteresis: a wave leaves the band of its previous tile only for a tile estimated more than h times as expensive (1 <= h <= 64, in steps of 1/256)
+extern "C" float ngp_render_set_band_hysteresis(float h) { return (float)rv_band_h_q8.exchange(rv_band_h_to_q8(h), std::memory_order_relaxed) * (1.0f / 256.0f); }
+// The pick as a wave of XCD `xcd` makes it, on the host: heads[n_bands] = rays handed out per band, dry_mask = bands the wave has seen dry, last_band =
+// the band of its previous tile or -1, perm / cost = the tile order and the estimates (both null: no estimates).  *band_out = the band, or -1 when none
+// has tiles left; *dry_mask_out (optional) = dry_mask with the bands this look found dry or empty.
+extern "C" int ngp_render_band_pick_host(const uint32_t* heads, uint32_t n_rays, const uint32_t* perm, const uint32_t* cost, uint32_t xcd, uint32_t dry_mask,
+                                         int last_band, float h, int* band_out, uint32_t* dry_mask_out) {
+    NGP_REQUIRE(heads && band_out && xcd < 8u && last_band >= -1 && last_band < (int)RV_BANDS && (perm == nullptr) == (cost == nullptr),
+                "band_pick_host: bad arguments");
+    unsigned long long best = 0ull;
+    for (uint32_t b = 0; b < RV_BANDS; b++) {
+        bool peek_dry = false;
+        best = ngp_band_better(best, ngp_band_look(b, xcd, RV_BANDS, n_rays, heads[b], dry_mask, last_band, rv_band_h_to_q8(h), perm, cost, &peek_dry));
+        if (peek_dry) dry_mask |= 1u << b;
+    }
+    if (dry_mask_out) *dry_mask_out = dry_mask;
+    *band_out = ngp_band_of_key(best, xcd, RV_BANDS);
+    return NGP_OK;
+}
 
 // Frame workspace: header (64 words: debug words of RV_COUNTERS builds | extent of the occupied blocks, words 26..31 | band queues, words 32..63) |
 // coarse occupancy map | the RV_TIMELINE build's histogram (8 KiB used) | tile order: queue position -> tile, then each tile's estimated cost, one u32
@@ -937,7 +986,7 @@ static int rv_render_frame(const ngp_field_t* field_host, const float* rays_o, c
 
     // coarse occupancy (needs Morton blocks: H a power of two >= 4) in the workspace, then in LDS
     F.coarse = nullptr; F.coarse_words = 0; F.skip = 0; F.occ_ext = nullptr; F.occ_unit = 0.0f; F.occ_top = 0.0f;
-    F.tile_perm = nullptr;
+    F.tile_perm = nullptr; F.tile_cost = nullptr; F.band_h_q8 = rv_band_h_q8.load(std::memory_order_relaxed);
     static_assert(sizeof(rf_lane_levels) * 4 == RV_LDS_LV, "LDS carve of the level table");
     size_t lds = RV_LDS_W + RV_LDS_SH + RV_LDS_LV + RV_LDS_SMP;
     const uint64_t blocks_per_level = (uint64_t)Hgrid * Hgrid * Hgrid / 64;
@@ -979,6 +1028,7 @@ static int rv_render_frame(const ngp_field_t* field_host, const float* rays_o, c
         hipLaunchKernelGGL(k_tile_sort, dim3(RV_BANDS), dim3(1024), 0, s, cost, n_tiles, perm);
         NGP_CHECK_LAUNCH("render_frame: tile order");
         F.tile_perm = perm;
+        if (rv_band_merge_enabled.load(std::memory_order_relaxed)) F.tile_cost = cost;
     }
     NGP_REQUIRE(lds <= 160 * 1024, "render_frame: LDS carve exceeds 160 KiB");
     // the raised dynamic-LDS limit is a per-device function attribute: set it once on every device this process renders on

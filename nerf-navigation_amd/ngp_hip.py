@@ -100,6 +100,9 @@ _SIGNATURES = {
     "ngp_render_set_block_skip": (c_int, [c_int]),
     "ngp_render_set_occupied_box": (c_int, [c_int]),
     "ngp_render_set_tile_order": (c_int, [c_int]),
+    "ngp_render_set_band_merge": (c_int, [c_int]),
+    "ngp_render_set_band_hysteresis": (c_f32, [c_f32]),
+    "ngp_render_band_pick_host": (c_int, [c_vp, c_u32, c_vp, c_vp, c_u32, c_u32, c_int, c_f32, c_vp, c_vp]),
     "ngp_field_train_set_two_pass": (c_int, [c_int]),
     "ngp_field_train_set_live_only": (c_int, [c_int]),
     "ngp_render_frame": (c_int, [c_vp, c_vp, c_vp, c_u32, c_u32, c_vp, c_f32, c_vp, c_u32, c_u32, c_f32, c_u32, c_vp,
@@ -247,6 +250,10 @@ def lib():
             handle.ngp_march_set_occupied_box(int(os.environ["NGP_OCC_BOX"]))
         if os.environ.get("NGP_TILE_ORDER") in ("0", "1"):               # ... of the frame kernel's cost-ordered tiles and bands
             handle.ngp_render_set_tile_order(int(os.environ["NGP_TILE_ORDER"]))
+        if os.environ.get("NGP_BAND_MERGE") in ("0", "1"):               # ... of the pick among an XCD's bands by their next tile's estimate
+            handle.ngp_render_set_band_merge(int(os.environ["NGP_BAND_MERGE"]))
+        if os.environ.get("NGP_BAND_HYSTERESIS"):                        # ... and of its hysteresis h (1..64)
+            handle.ngp_render_set_band_hysteresis(float(os.environ["NGP_BAND_HYSTERESIS"]))
         if os.environ.get("NGP_FT_LIVE_ONLY") in ("0", "1"):             # ... of the training backward (live samples only | all samples)
             handle.ngp_field_train_set_live_only(int(os.environ["NGP_FT_LIVE_ONLY"]))
     return _lib

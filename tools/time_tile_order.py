@@ -1,5 +1,6 @@
-"""The frame kernel's tile order on and off (ngp_render_set_tile_order), ms per 800x800 frame of the hand-set scene for a camera on bench's orbit,
-one below the scene and one above it:  python tools/time_tile_order.py [frames] [res]
+"""The frame kernel's tile order off and on (ngp_render_set_tile_order), and with it the pick among an XCD's bands by their next tile's estimate
+(ngp_render_set_band_merge; NGP_BAND_HYSTERESIS sets its h): ms per 800x800 frame of the hand-set scene for a camera on bench's orbit, one below the
+scene and one above it:  python tools/time_tile_order.py [frames] [res]
 Each (pose, setting) is timed twice, interleaved, with HIP events around every launch (mean of the launches after 5 warm-up frames)."""
 import importlib
 import os
@@ -27,8 +28,12 @@ L = ngp_hip.lib()
 poses = {"orbit(1)": W.orbit_pose(1), "below(z=-1.2)": W.orbit_pose(1, height=-1.2), "above(z=1.5)": W.orbit_pose(1, height=1.5)}
 
 
-def time_pose(pose, order):
+SETTINGS = {"row-major": (0, 0), "cost order": (1, 0), "cost order + band merge": (1, 1)}       # (tile order, band merge)
+
+
+def time_pose(pose, order, merge):
     previous = L.ngp_render_set_tile_order(order)
+    previous_merge = L.ngp_render_set_band_merge(merge)
     try:
         for _ in range(5):
             ren.render_fused_camera(pose, intr, res, res, bg_color=1)
@@ -42,14 +47,16 @@ def time_pose(pose, order):
         torch.cuda.synchronize()
     finally:
         L.ngp_render_set_tile_order(previous)
+        L.ngp_render_set_band_merge(previous_merge)
     return float(np.mean([a.elapsed_time(b) for a, b in ev])), int(out["stats"][0])
 
 
 for name, pose in poses.items():
-    t = {0: [], 1: []}
+    t = {k: [] for k in SETTINGS}
     for _ in range(2):
-        for order in (0, 1):
-            ms, smp = time_pose(pose, order)
-            t[order].append(ms)
-    print("%-14s samples %9d  row-major %s ms  cost order %s ms  (%+.1f %%)" % (
-        name, smp, " / ".join("%.3f" % v for v in t[0]), " / ".join("%.3f" % v for v in t[1]), 100.0 * (np.mean(t[1]) / np.mean(t[0]) - 1.0)))
+        for k, (order, merge) in SETTINGS.items():
+            ms, smp = time_pose(pose, order, merge)
+            t[k].append(ms)
+    base = np.mean(t["row-major"])
+    print("%-14s samples %9d  " % (name, smp) + "  ".join(
+        "%s %s ms%s" % (k, " / ".join("%.3f" % v for v in t[k]), "" if k == "row-major" else " (%+.1f %%)" % (100.0 * (np.mean(t[k]) / base - 1.0))) for k in SETTINGS))
