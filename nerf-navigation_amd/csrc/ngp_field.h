@@ -129,9 +129,14 @@ __device__ __forceinline__ void rf_gather_pair(const rf_params& P, const rf_lane
     #pragma unroll
     for (int i = 2 * H; i < 2 * H + 2; i++) {
         const float px = ppx[i & 1], py = ppy[i & 1], pz = ppz[i & 1];
-        const float flx = floorf(px), fly = floorf(py), flz = floorf(pz);
-        const uint32_t gx = (uint32_t)flx, gy = (uint32_t)fly, gz = (uint32_t)flz;
-        fx[i & 1] = px - flx; fy[i & 1] = py - fly; fz[i & 1] = pz - flz;        // == px - (float)gx: the floor is an exact small integer
+        // Cell and fraction (gridencoder.cu:133-135: floorf, the conversion of the floor, pos - floor) without the floor.  The normalised position
+        // is in [0, 1] (INRANGE, or rf_encode moved an outside point to 0), so p = x * scale + 0.5 >= 0.5:
+        //  * the conversion truncates toward zero, which is the floor of a p >= 0: the same cell;
+        //  * p - floor(p) is a multiple of ulp(p) below 1 and was never rounded; v_fract_f32 returns exactly that value, its clamp to
+        //    0x3f7fffff = 1 - 2^-24 being the largest fraction a binary32 p >= 0.5 can have;
+        //  * a NaN position gives cell 0 and a NaN fraction in both forms.
+        const uint32_t gx = (uint32_t)px, gy = (uint32_t)py, gz = (uint32_t)pz;
+        fx[i & 1] = __builtin_amdgcn_fractf(px); fy[i & 1] = __builtin_amdgcn_fractf(py); fz[i & 1] = __builtin_amdgcn_fractf(pz);
         const uint32_t bit = 1u << i;
         if (cls.dense & bit) {
             // x + y*s1 + z*s2 (always < size); the x-neighbour is the next row: one 8-byte load per (y, z)

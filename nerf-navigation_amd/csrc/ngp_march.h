@@ -1,13 +1,47 @@
 // ngp_march.h -- the march arithmetic shared by the per-op kernels (raymarching.hip, through ngp_march_t in ngp_device.h's
 // successor below) and the fused frame kernel (render_fused.hip): one sample point, the step out of an empty cell, and the
-// verified skip through an empty block.  Templates over the "view" type V, which provides the ray (ox..dz, rdx..rdz) and the
-// march constants (bound, rbound, dt_gamma, dt_min, dt_max, rH, Hf, Hm1, mip()).
+// verified skip through an empty block.  Templates over the "view" type V, which provides the ray (ox..dz, rdx..rdz), the
+// march constants (bound, rbound, dt_gamma, dt_min, dt_max, rH, Hf, Hm1, mip()) and the compile-time property
+// V::pow2_grid: true when the view is only ever built for a grid size H that is a power of two; such a view also provides
+// hHf = 0.5 * Hf and r2H = 2 * rH (both exact), and the scalings by H below take their one-multiply forms.
 #pragma once
 #include "ngp_device.h"
 
 #ifndef NGP_SKIP_WALK
 #define NGP_SKIP_WALK 32               // dt_gamma > 0: steps a skip may walk (a varying step has no closed form)
 #endif
+
+// The three places where the reference scales by the grid size, each stated once in both forms.  With H = 2^k every factor
+// below is a power of two, so each multiplication only moves the exponent: the one-multiply form has the reference's bits as
+// long as nothing overflows or underflows, which the comments bound.  A view with any H keeps the reference's sequence.
+//
+// cell coordinate of u = x / mip_bound + 1 (raymarching.cu:775-777): u is in [0, 2] and is either 0 or at least 2^-24 (the sum
+// of 1 and a number of magnitude <= 1 is a multiple of 2^-24), so u * 0.5 * H is exact in both groupings.
+template <class V>
+__device__ __forceinline__ float ngp_cell_coord(const V& m, float u) {
+    if constexpr (V::pow2_grid) return u * m.hHf;
+    else return (u * 0.5f) * m.Hf;
+}
+// the step in cells, (dt * H) * 0.5, whose exponent picks the cascade (raymarching.cu:768): dt >= dt_min is a normal number far
+// from either end of the range, so both groupings are exact.
+template <class V>
+__device__ __forceinline__ float ngp_step_cells(const V& m, float dt) {
+    if constexpr (V::pow2_grid) return dt * m.hHf;
+    else return (dt * m.Hf) * 0.5f;
+}
+// the plane of cell face c (a whole number, 0 <= c <= H) in [-1, 1]: (c / H) * 2 - 1 (raymarching.cu:793-795).  With H = 2^k the
+// product c * (2 / H) is exact, so the fused multiply-add rounds the same difference the separate subtraction rounds.
+template <class V>
+__device__ __forceinline__ float ngp_face_plane(const V& m, float c) {
+    if constexpr (V::pow2_grid) return __builtin_fmaf(c, m.r2H, -1.0f);
+    else return (c * m.rH) * 2.0f - 1.0f;
+}
+// The face a ray leaves cell n through, as a cell count: the reference's (float)n + 0.5f + 0.5f * copysignf(1, d) is n + 1 for a
+// direction with a clear sign bit and n for a set one (-0 and NaNs by their sign bit, as copysignf reads them); every term and
+// both sums are exact (n < 2^23), so it is (float)(n + s), s = 1 - signbit(d): two integer operations and one conversion.
+__device__ __forceinline__ float ngp_exit_face(int n, float d) {
+    return (float)(n + 1 + (__builtin_bit_cast(int, d) >> 31));
+}
 
 // One march sample point: everything kernel_march_rays derives from t (raymarching.cu:748-781), same arithmetic.
 template <class V>
@@ -21,30 +55,30 @@ struct ngp_point {
         dt = ngp_clampf(tc * m.dt_gamma, m.dt_min, m.dt_max);
         int e_pos, e_dt;
         (void)frexpf(fmaxf(fabsf(x), fmaxf(fabsf(y), fabsf(z))), &e_pos);
-        (void)frexpf((dt * m.Hf) * 0.5f, &e_dt);
+        (void)frexpf(ngp_step_cells(m, dt), &e_dt);
         const int lp = m.mip(e_pos), ld = m.mip(e_dt);
         level = lp > ld ? lp : ld;
         const float p2 = (float)(1 << level);
         mip_bound = fminf(p2, m.bound);
         // 1 / mip_bound without a division per probe: 2^-level is exact and 1 / bound is the same IEEE quotient, computed once
         const float mip_rbound = (p2 <= m.bound) ? __builtin_ldexpf(1.0f, -level) : m.rbound;
-        nx = (int)ngp_clampf(((x * mip_rbound + 1.0f) * 0.5f) * m.Hf, 0.0f, m.Hm1);
-        ny = (int)ngp_clampf(((y * mip_rbound + 1.0f) * 0.5f) * m.Hf, 0.0f, m.Hm1);
-        nz = (int)ngp_clampf(((z * mip_rbound + 1.0f) * 0.5f) * m.Hf, 0.0f, m.Hm1);
+        nx = (int)ngp_clampf(ngp_cell_coord(m, x * mip_rbound + 1.0f), 0.0f, m.Hm1);
+        ny = (int)ngp_clampf(ngp_cell_coord(m, y * mip_rbound + 1.0f), 0.0f, m.Hm1);
+        nz = (int)ngp_clampf(ngp_cell_coord(m, z * mip_rbound + 1.0f), 0.0f, m.Hm1);
     }
     // ray parameter at which the ray leaves this point's cell (raymarching.cu:792-797)
     __device__ __forceinline__ float cell_exit(const V& m, float tc) const {
-        const float tx = (((((float)nx + 0.5f + 0.5f * copysignf(1.0f, m.dx)) * m.rH) * 2.0f - 1.0f) * mip_bound - x) * m.rdx;
-        const float ty = (((((float)ny + 0.5f + 0.5f * copysignf(1.0f, m.dy)) * m.rH) * 2.0f - 1.0f) * mip_bound - y) * m.rdy;
-        const float tz = (((((float)nz + 0.5f + 0.5f * copysignf(1.0f, m.dz)) * m.rH) * 2.0f - 1.0f) * mip_bound - z) * m.rdz;
+        const float tx = (ngp_face_plane(m, ngp_exit_face(nx, m.dx)) * mip_bound - x) * m.rdx;
+        const float ty = (ngp_face_plane(m, ngp_exit_face(ny, m.dy)) * mip_bound - y) * m.rdy;
+        const float tz = (ngp_face_plane(m, ngp_exit_face(nz, m.dz)) * mip_bound - z) * m.rdz;
         return tc + fmaxf(0.0f, fminf(tx, fminf(ty, tz)));
     }
     // the same for the aligned block of 2^sh cells per axis around the cell (an estimate: only used to choose a skip target)
     __device__ __forceinline__ float block_exit(const V& m, float tc, int sh) const {
         const float bs = (float)(1 << sh);
-        const float tx = ((((((float)(nx >> sh) + 0.5f + 0.5f * copysignf(1.0f, m.dx)) * bs) * m.rH) * 2.0f - 1.0f) * mip_bound - x) * m.rdx;
-        const float ty = ((((((float)(ny >> sh) + 0.5f + 0.5f * copysignf(1.0f, m.dy)) * bs) * m.rH) * 2.0f - 1.0f) * mip_bound - y) * m.rdy;
-        const float tz = ((((((float)(nz >> sh) + 0.5f + 0.5f * copysignf(1.0f, m.dz)) * bs) * m.rH) * 2.0f - 1.0f) * mip_bound - z) * m.rdz;
+        const float tx = (ngp_face_plane(m, ngp_exit_face(nx >> sh, m.dx) * bs) * mip_bound - x) * m.rdx;
+        const float ty = (ngp_face_plane(m, ngp_exit_face(ny >> sh, m.dy) * bs) * mip_bound - y) * m.rdy;
+        const float tz = (ngp_face_plane(m, ngp_exit_face(nz >> sh, m.dz) * bs) * mip_bound - z) * m.rdz;
         return tc + fmaxf(0.0f, fminf(tx, fminf(ty, tz)));
     }
 };
@@ -85,7 +119,9 @@ __device__ __forceinline__ float ngp_lattice_jump(float t, float dtc, float lim)
     (void)frexpf(t, &e);                               // t in [2^(e-1), 2^e), ulp 2^(e-24)
     const float end = fminf(lim, __builtin_ldexpf(1.0f, e));
     const float err = dtc - du;                        // exact: rounding error of t + dtc
-    if (!(t1 < end) || !(du > 0.0f) || fabsf(err) == __builtin_ldexpf(1.0f, e - 25)) return t1;
+    // t = 0 (a march that starts at the eye: min_near 0) lies in no binade: frexpf gives e = 0, and the multiples of the step up
+    // to 1 cross a dozen binades, each sum rounding on its own.  Only the real step is taken from there.
+    if (!(t > 0.0f) || !(t1 < end) || !(du > 0.0f) || fabsf(err) == __builtin_ldexpf(1.0f, e - 25)) return t1;
     // j <= (end - t1) / du - 1 keeps t1 + j du below `end` whatever the rounding of the estimate (relative error ~1e-6)
     const float j = floorf((end - t1) * __builtin_amdgcn_rcpf(du)) - 1.0f;
     return j > 0.0f ? t1 + j * du : t1;                // j du < 2^(e-1) is a multiple of u: both operations exact
@@ -208,6 +244,7 @@ __host__ __device__ inline bool ngp_skip_allowed(uint32_t C, uint32_t H, float b
 // found by OR-ing its 64 words (512 contiguous bytes) once per block entered.
 // ---------------------------------------------------------------------------
 struct ngp_march_t {
+    static constexpr bool pow2_grid = false;   // any H: the scalings by H keep the reference's form (ngp_cell_coord and its kin)
     float ox, oy, oz, dx, dy, dz, rdx, rdy, rdz;
     float bound, rbound, dt_gamma, dt_min, dt_max, rH, H3, Hf, Cf, Hm1;
     const uint8_t* grid;
@@ -250,6 +287,9 @@ struct ngp_march_t {
         if (blocks_per_level && ngp_skip_allowed(C, H, bound)) skip_M = ngp_skip_margin(*this, bound, far);
     }
 
+    // The reference's clamp (raymarching.cu:767).  (float)e is exact for every exponent and C - 1 is a small whole number, so
+    // min(max(e, 0), C - 1) in integers picks the same value; the frame kernel's view clamps that way (rv_consts::mip).  Here the
+    // integer form lifts k_march_train_count from 110 to 134 registers (profiles/HISTORY.md 5.9), so the per-op kernels keep this one.
     __device__ __forceinline__ int mip(int e) const {
         return (int)fminf(Cf - 1.0f, fmaxf(0.0f, (float)e));
     }

@@ -174,9 +174,13 @@ __global__ __launch_bounds__(256) void k_build_coarse(const uint8_t* __restrict_
 // The march state of ngp_march_t split in two so that only what differs per ray occupies VGPRs:
 struct rv_ray { float ox, oy, oz, dx, dy, dz, rdx, rdy, rdz; };
 struct rv_consts {                                     // wave-uniform (SGPRs), same formulas as ngp_march_t::setup
-    float bound, rbound, dt_gamma, dt_min, dt_max, rH, H3, Hf, Cf, Hm1;
+    // The frame launcher requires a power-of-two H (rv_render_frame), so this view takes the one-multiply forms of ngp_march.h:
+    // hHf = 0.5 * H and r2H = 2 / H, both powers of two.
+    static constexpr bool pow2_grid = true;
+    float bound, rbound, dt_gamma, dt_min, dt_max, H3, hHf, r2H, Hm1;
+    int Cm1;                                           // C - 1: the exponent is clamped in integers, which picks the same value (ngp_march_t::mip)
     const uint8_t* grid;
-    __device__ __forceinline__ int mip(int e) const { return (int)fminf(Cf - 1.0f, fmaxf(0.0f, (float)e)); }
+    __device__ __forceinline__ int mip(int e) const { return min(max(e, 0), Cm1); }
 };
 __device__ __forceinline__ float rv_uniform(float v) {     // a wave-uniform value computed by the vector ALU -> SGPR
     return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
@@ -393,11 +397,12 @@ __device__ __forceinline__ void rv_frame_loop(const rf_params& P, const rf_frame
     // float conversions and divisions run on the vector ALU even for uniform inputs; rv_uniform moves the results to SGPRs
     rv_consts K;
     K.bound = P.bound; K.rbound = rv_uniform(1.0f / P.bound); K.dt_gamma = F.dt_gamma;
-    K.Hf = rv_uniform((float)F.H); K.Cf = rv_uniform((float)F.C); K.Hm1 = rv_uniform((float)(F.H - 1));
-    K.rH = rv_uniform(1.0f / K.Hf);
+    const float Hf = rv_uniform((float)F.H);
+    K.hHf = rv_uniform(0.5f * Hf); K.Cm1 = (int)F.C - 1; K.Hm1 = rv_uniform((float)(F.H - 1));
+    K.r2H = rv_uniform(2.0f * (1.0f / Hf));
     K.H3 = rv_uniform((float)(F.H * F.H * F.H));
     K.dt_min = rv_uniform((2.0f * 1.7320508075688772f) / (float)F.max_steps);
-    K.dt_max = rv_uniform(((2.0f * 1.7320508075688772f) * (float)(1 << (F.C - 1))) / K.Hf);
+    K.dt_max = rv_uniform(((2.0f * 1.7320508075688772f) * (float)(1 << (F.C - 1))) / Hf);
     K.grid = F.bitfield;
 
     bool active = false;
@@ -522,7 +527,7 @@ __device__ __forceinline__ void rv_frame_loop(const rf_params& P, const rf_frame
             // the same for the march constants: uniform, but the scalar registers are all taken, so they live in (spilled)
             // vector registers; a copy per round keeps every memory access out of the probe loop
             rv_consts Kr = K;
-            asm("" : "+v"(Kr.Hf), "+v"(Kr.Hm1), "+v"(Kr.Cf), "+v"(Kr.rH), "+v"(Kr.dt_min), "+v"(Kr.dt_max), "+v"(Kr.rbound), "+v"(Kr.H3));
+            asm("" : "+v"(Kr.hHf), "+v"(Kr.Hm1), "+v"(Kr.Cm1), "+v"(Kr.r2H), "+v"(Kr.dt_min), "+v"(Kr.dt_max), "+v"(Kr.rbound), "+v"(Kr.H3));
             // (the margin bounds rounding errors by the largest ray parameter in play: the march limit may have been pulled in to the occupied box, the
             //  points a skip evaluates lie at most one cascade further)
             const float M = (active && F.skip) ? ngp_skip_margin(mr, K.bound, lds_occ ? far_r + 4.0f * K.bound : far_r) : __builtin_inff();
@@ -795,9 +800,10 @@ __global__ __launch_bounds__(256) void k_tile_cost(rf_frame F, float bound, uint
     if (tile >= n_tiles) return;
     rv_consts K;
     K.bound = bound; K.rbound = 1.0f / bound; K.dt_gamma = F.dt_gamma;
-    K.Hf = (float)F.H; K.Cf = (float)F.C; K.Hm1 = (float)(F.H - 1); K.rH = 1.0f / K.Hf; K.H3 = (float)(F.H * F.H * F.H);
+    const float Hf = (float)F.H;
+    K.hHf = 0.5f * Hf; K.Cm1 = (int)F.C - 1; K.Hm1 = (float)(F.H - 1); K.r2H = 2.0f * (1.0f / Hf); K.H3 = (float)(F.H * F.H * F.H);
     K.dt_min = (2.0f * 1.7320508075688772f) / (float)F.max_steps;
-    K.dt_max = ((2.0f * 1.7320508075688772f) * (float)(1 << (F.C - 1))) / K.Hf;
+    K.dt_max = ((2.0f * 1.7320508075688772f) * (float)(1 << (F.C - 1))) / Hf;
     K.grid = F.bitfield;
     float box[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};  // the occupied box as the frame kernel forms it (k_render_frame_multi's prologue)
     if (F.occ_ext) {
