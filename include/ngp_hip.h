@@ -527,6 +527,33 @@ int ngp_nav_run_backward(const ngp_nav_field_t* field_host, const void* prepared
                          const float* grad_image, const float* grad_depth, const float* grad_weights_sum, const void* saved, size_t saved_bytes,
                          float* grad_rays_o, float* grad_rays_d, void* stream);
 
+/* One whole frame of NeRFRenderer.run_cuda's inference branch (nerf/renderer.py:325-374) of the DEFAULT float32 field in one launch
+ * (csrc/nav_frame.hip): ngp_render_frame for the model above, float32 throughout.  The semantics are ngp_render_frame's, word for
+ * word: one resumable march per ray from `near`, at most max_steps samples per ray, a ray stops after the sample whose incoming T is below 1e-4,
+ * sigma is multiplied by field_host->density_scale before alpha; image [N,3], depth [N], weights_sum [N] f32 are fully written, the background mix
+ * and the depth map applied (depth is NaN where far == near); aabb [6] and bg_color [3] on the host.
+ * stats [4] u32 device (zeroed by the call): [0] ray-samples composited, [1] rays cut short by the max_steps cap, [2] rays with at least one sample,
+ * [3] ray-samples whose field was evaluated: [0] plus what rays had marched behind the sample that saturated them (at most 2 per ray); unlike
+ * [0..2] it is a property of the kernel's rounds, not of the frame.
+ * image_width: a traversal hint as for ngp_render_frame (8x8 pixel tiles); results do not depend on it, bit for bit.  Two launches of the same
+ * frame are bit-identical.  prepared: ngp_nav_field_prepare's workspace.  workspace: ngp_nav_render_frame_workspace(N) bytes, NGP_EWORKSPACE below
+ * that.  Hgrid: a power of two, NGP_EINVAL otherwise.  Every refusal (those of the queries above included) happens before anything reaches the device. */
+size_t ngp_nav_render_frame_workspace(uint32_t N);
+int ngp_nav_render_frame(const ngp_nav_field_t* field_host, const void* prepared,
+                         const float* rays_o, const float* rays_d, uint32_t N, uint32_t image_width,
+                         const float* aabb_host, float min_near, const uint8_t* bitfield, uint32_t C, uint32_t Hgrid,
+                         float dt_gamma, uint32_t max_steps, const float* bg_color3_host,
+                         float* image, float* depth, float* weights_sum, uint32_t* stats,
+                         void* workspace, size_t workspace_bytes, void* stream);
+/* The same frame for the H x W rays of one camera (pose, intrinsics: host, as for ngp_get_rays below), generated inside the kernel:
+ * bit-identical to ngp_get_rays followed by ngp_nav_render_frame with image_width = W. */
+int ngp_nav_render_frame_camera(const ngp_nav_field_t* field_host, const void* prepared,
+                                const float* pose_host, const float* intrinsics_host, uint32_t H, uint32_t W,
+                                const float* aabb_host, float min_near, const uint8_t* bitfield, uint32_t C, uint32_t Hgrid,
+                                float dt_gamma, uint32_t max_steps, const float* bg_color3_host,
+                                float* image, float* depth, float* weights_sum, uint32_t* stats,
+                                void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- camera rays (reference: get_rays, nerf/utils.py:53-116) ----
  * pose: host, row-major 4x4 (or the first 3 rows of it) camera-to-world; intrinsics: host [4] = fx, fy, cx, cy.
  * Ray k is that of pixel inds[k] (device int64, row-major pixel index, the `inds` of the reference's random branches) or

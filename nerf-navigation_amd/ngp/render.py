@@ -3,7 +3,8 @@
 Three render paths:
   run_cuda(...)      the reference's occupancy-grid path, op by op (nerf/renderer.py:257-379): the parity anchor and
                      what a torch-ngp caller gets from the drop-in packages;
-  render_fused(...)  one launch per frame (csrc/render_fused.hip) -- the MI355X-native fast path for inference;
+  render_fused(...)  one launch per frame (csrc/render_fused.hip for NGPFieldFF, csrc/nav_frame.hip for the default float32 NGPField) -- the
+                     MI355X-native fast path for inference;
   run(...)           the fixed-step path used by the nav loop (nerf/renderer.py:125-254, simulate.py:163-166).
 plus update_extra_state / mark_untrained_grid (density-grid maintenance, nerf/renderer.py:381-537) on the native ops of
 csrc/density_grid.hip.
@@ -230,15 +231,60 @@ class NGPRenderer(nn.Module):
     # ------------------------------------------------------------------------------------------------------------
     # one launch per frame
     # ------------------------------------------------------------------------------------------------------------
+    def _default_frame_field(self, what):
+        """The holder (ngp.nav._NativeField: ngp_nav_field_t + prepared weights, re-prepared when a parameter changes) of a default float32
+        NGPField for the one-launch frame of csrc/nav_frame.hip; a ValueError that names the reason for everything that frame does not render."""
+        from . import nav as _nav
+        if not self.cuda_ray:
+            raise ValueError(f"{what}: this renderer was built with cuda_ray=False: it has no occupancy grid for the frame kernel to march (use run())")
+        if self.bg_radius > 0 or getattr(self.field, "bg_radius", -1) > 0:
+            raise ValueError(f"{what}: bg_radius > 0: the one-launch frame mixes in a constant background colour, not a background model (use run_cuda)")
+        holder = self.__dict__.get("_default_frame_holder")
+        if holder is None or holder.field is not self.field:
+            try:
+                holder = _nav._NativeField(self)
+            except (RuntimeError, AttributeError) as e:
+                raise ValueError(f"{what}: the one-launch frame renders NGPFieldFF, or the default float32 NGPField (hash grid 16 x 2 float32, Linear "
+                                 f"32-64-16 | 31-64-64-3); {type(self.field).__name__} is neither ({e})") from None
+            self.__dict__["_default_frame_holder"] = holder               # (not a module attribute: the holder points back at this renderer)
+        return holder
+
+    def _render_default_frame(self, what, N, device, dt_gamma, bg_color, max_steps, launch):
+        """the launch of ngp_nav_render_frame[_camera] around `launch(L, struct, prepared, tail...)`: outputs, host arguments, workspace"""
+        holder = self._default_frame_field(what)
+        image = torch.empty(N, 3, dtype=torch.float32, device=device)
+        depth = torch.empty(N, dtype=torch.float32, device=device)
+        weights_sum = torch.empty(N, dtype=torch.float32, device=device)
+        stats = torch.empty(4, dtype=torch.int32, device=device)
+        if bg_color is None:
+            bg_color = 1
+        bg = (ctypes.c_float * 3)(*([float(bg_color)] * 3 if np.isscalar(bg_color) else [float(v) for v in bg_color]))
+        aabb = (ctypes.c_float * 6)(*[float(v) for v in self._aabb().tolist()])
+        L = _hip.lib()
+        ws = _hip.workspace(L.ngp_nav_render_frame_workspace(N), device)
+        with torch.cuda.device(device):
+            st, prep = holder.struct()
+            tail = (aabb, self.min_near, _hip.ptr(self.density_bitfield), self.cascade, self.grid_size, dt_gamma, max_steps, bg,
+                    _hip.ptr(image), _hip.ptr(depth), _hip.ptr(weights_sum), _hip.ptr(stats), _hip.ptr(ws), ws.numel(), _hip.stream())
+            _hip.check(launch(L, ctypes.byref(st), _hip.ptr(prep), tail), what)
+        return image, depth, weights_sum, stats
+
     @torch.no_grad()
     def render_fused(self, rays_o, rays_d, dt_gamma=0, bg_color=None, max_steps=1024, image_width=0, **kwargs):
         """Inference only.  Returns image / depth / weights_sum like run_cuda plus `stats`, a 4-int device tensor:
         [ray-samples evaluated, rays that hit the max_steps cap, rays with >= 1 sample, 16-column MFMA tiles evaluated].
-        image_width: width of the image when the rays are a full row-major image (enables 8x8 tile traversal)."""
+        image_width: width of the image when the rays are a full row-major image (enables 8x8 tile traversal).
+        The field is an NGPFieldFF (csrc/render_fused.hip, half precision) or a default float32 NGPField (csrc/nav_frame.hip, float32 throughout;
+        there stats[3] counts the ray-samples whose field was evaluated); anything else raises a ValueError that says why."""
         prefix = rays_o.shape[:-1]
         rays_o = rays_o.contiguous().view(-1, 3).float()
         rays_d = rays_d.contiguous().view(-1, 3).float()
         N, device = rays_o.shape[0], rays_o.device
+        if not hasattr(self.field, "fused_state"):              # the default float32 field: csrc/nav_frame.hip (stats[3]: ray-samples evaluated)
+            image, depth, weights_sum, stats = self._render_default_frame(
+                "render_fused", N, device, dt_gamma, bg_color, max_steps,
+                lambda L, st, prep, tail: L.ngp_nav_render_frame(st, prep, _hip.ptr(rays_o), _hip.ptr(rays_d), N, int(image_width), *tail))
+            return {"image": image.view(*prefix, 3), "depth": depth.view(*prefix), "weights_sum": weights_sum, "stats": stats}
         image = torch.empty(N, 3, dtype=torch.float32, device=device)
         depth = torch.empty(N, dtype=torch.float32, device=device)
         weights_sum = torch.empty(N, dtype=torch.float32, device=device)
@@ -264,6 +310,13 @@ class NGPRenderer(nn.Module):
         """render_fused for the H x W rays of one camera (pose [4,4] or [3,4] cam2world, intrinsics fx, fy, cx, cy) without
         materialising them: get_rays (nerf/utils.py:53-116) runs inside the frame kernel.  Same results, bit for bit, as
         `render_fused(*get_rays_native(...), image_width=W)`."""
+        if not hasattr(self.field, "fused_state"):              # the default float32 field: csrc/nav_frame.hip
+            device = next(self.field.parameters()).device
+            pose_h, intr_h = _hip.camera_args(pose, intrinsics)
+            image, depth, weights_sum, stats = self._render_default_frame(
+                "render_fused_camera", int(H) * int(W), device, dt_gamma, bg_color, max_steps,
+                lambda L, st, prep, tail: L.ngp_nav_render_frame_camera(st, prep, pose_h, intr_h, int(H), int(W), *tail))
+            return {"image": image.view(H, W, 3), "depth": depth.view(H, W), "weights_sum": weights_sum, "stats": stats}
         device = self.density_bitfield.device
         N = int(H) * int(W)
         image = torch.empty(N, 3, dtype=torch.float32, device=device)
@@ -289,6 +342,9 @@ class NGPRenderer(nn.Module):
         """P frames in ONE launch (ngp_render_frames_camera): poses [P,4,4] cam2world (tensor, array or nested lists), one set of intrinsics.
         The frame kernel's ramp and drain are paid once per launch instead of once per frame; every pixel equals `render_fused_camera`'s, bit
         for bit.  Returns image [P,H,W,3], depth [P,H,W], weights_sum [P,H*W], stats (summed over the frames)."""
+        if not hasattr(self.field, "fused_state"):
+            raise ValueError("render_fused_cameras: several poses per launch are built for NGPFieldFF only; render a default float32 NGPField pose by "
+                             "pose with render_fused_camera")
         device = self.density_bitfield.device
         if isinstance(poses, torch.Tensor):
             poses = poses.detach().cpu().numpy()

@@ -116,6 +116,11 @@ _SIGNATURES = {
     "ngp_nav_run_saved_bytes": (c_sz, [c_u32, c_u32]),
     "ngp_nav_run_forward": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_u32, c_u32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "ngp_nav_run_backward": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_u32, c_u32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp, c_vp, c_vp]),
+    "ngp_nav_render_frame_workspace": (c_sz, [c_u32]),
+    "ngp_nav_render_frame": (c_int, [c_vp, c_vp, c_vp, c_vp, c_u32, c_u32, c_vp, c_f32, c_vp, c_u32, c_u32, c_f32, c_u32, c_vp,
+                                     c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "ngp_nav_render_frame_camera": (c_int, [c_vp, c_vp, c_vp, c_vp, c_u32, c_u32, c_vp, c_f32, c_vp, c_u32, c_u32, c_f32, c_u32, c_vp,
+                                            c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "ngp_get_rays": (c_int, [c_vp, c_vp, c_u32, c_u32, c_vp, c_u32, c_vp, c_vp, c_vp]),
     "ngp_render_frame_camera": (c_int, [c_vp, c_vp, c_vp, c_u32, c_u32, c_vp, c_f32, c_vp, c_u32, c_u32, c_f32, c_u32, c_vp,
                                         c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
