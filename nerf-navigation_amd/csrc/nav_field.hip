@@ -267,18 +267,21 @@ __device__ __forceinline__ float nv_block_sum(float v, float* __restrict__ lds4)
     return (lds4[0] + lds4[1]) + (lds4[2] + lds4[3]);
 }
 
-// alpha and the transmittance factor of one sample (:208-209)
-__device__ __forceinline__ void nv_alpha(float delta, float scale, float sigma, float& alpha, float& keep) {
-    alpha = 1.0f - expf(-delta * scale * sigma);
+// alpha and the transmittance factor of one sample (:208-209); ex = exp(-delta scale sigma), the number alpha was rounded from
+__device__ __forceinline__ void nv_alpha(float delta, float scale, float sigma, float& ex, float& alpha, float& keep) {
+    ex = expf(-delta * scale * sigma);
+    alpha = 1.0f - ex;
     keep = 1.0f - alpha + 1e-15f;
 }
 
 // What the forward leaves for the backward, one record per sample, stored word-major ([word][N*T]: the lanes of a wave are consecutive
-// samples, so every word is a coalesced 256-byte store): the density net's 16 outputs, its ReLU mask, alpha and the transmittance in
-// front of the sample, the colour and the colour net's two ReLU masks.  108 bytes per sample (57 MB for 1,024 rays x 512 steps)
+// samples, so every word is a coalesced 256-byte store): the density net's 16 outputs, its ReLU mask, exp(-delta scale sigma) and the
+// transmittance in front of the sample, the colour and the colour net's two ReLU masks.  108 bytes per sample (57 MB for 1,024 rays x 512 steps)
 // instead of recomputing two encoder passes and both networks in the backward.
 static constexpr uint32_t NV_REC_WORDS = 27;
-enum { NV_R_OUT = 0, NV_R_RELU = 16, NV_R_ALPHA = 18, NV_R_TR = 19, NV_R_RGB = 20, NV_R_MA = 23, NV_R_MB = 25 };
+// NV_R_EX and not alpha: alpha = 1 - ex is recomputed from it bit for bit, but ex cannot be recovered from alpha -- 1 - alpha has an ABSOLUTE error of
+// 2^-25, which for an opaque sample (ex = 1e-4) is 3e-4 of d alpha / d sigma = delta scale ex, and that sample is the one the ray's gradient hangs on
+enum { NV_R_OUT = 0, NV_R_RELU = 16, NV_R_EX = 18, NV_R_TR = 19, NV_R_RGB = 20, NV_R_MA = 23, NV_R_MB = 25 };
 
 __global__ __launch_bounds__(NV_BLOCK) void k_nav_run_fwd(nav_params P, nav_run R, float* __restrict__ image, float* __restrict__ depth,
                                                           float* __restrict__ weights_sum, uint32_t* __restrict__ save) {
@@ -299,8 +302,8 @@ __global__ __launch_bounds__(NV_BLOCK) void k_nav_run_fwd(nav_params P, nav_run 
         const bool inside = nv_normalise(P, s.px, s.py, s.pz, x0, x1, x2);
         float out[16];
         const uint64_t relu = nv_density_forward<NV_RUN_U>(P, inside, x0, x1, x2, col, out);
-        float alpha, keep;
-        nv_alpha(s.znext_minus_z, P.density_scale, expf(out[0]), alpha, keep);
+        float ex, alpha, keep;
+        nv_alpha(s.znext_minus_z, P.density_scale, expf(out[0]), ex, alpha, keep);
         if (!live) { alpha = 0.0f; keep = 1.0f; }
         float total;
         const float Tr = carry * nv_block_excl_product(keep, lds4, total);
@@ -310,7 +313,7 @@ __global__ __launch_bounds__(NV_BLOCK) void k_nav_run_fwd(nav_params P, nav_run 
             #pragma unroll
             for (int m = 0; m < 16; m++) q[(NV_R_OUT + m) * NT] = __float_as_uint(out[m]);
             q[NV_R_RELU * NT] = (uint32_t)relu; q[(NV_R_RELU + 1) * NT] = (uint32_t)(relu >> 32);
-            q[NV_R_ALPHA * NT] = __float_as_uint(alpha); q[NV_R_TR * NT] = __float_as_uint(Tr);
+            q[NV_R_EX * NT] = __float_as_uint(ex); q[NV_R_TR * NT] = __float_as_uint(Tr);
         }
         float rgb[3] = {0.0f, 0.0f, 0.0f};
         uint64_t ma = 0, mb = 0;
@@ -390,7 +393,8 @@ __global__ __launch_bounds__(NV_BLOCK) void k_nav_run_bwd(nav_params P, nav_run 
         const bool live = i < R.T;
         const nv_sample s = nv_sample_at(R, live ? i : R.T - 1, near, far, ox, oy, oz, dx, dy, dz);
         const uint32_t* q = save + (size_t)n * R.T + (live ? i : R.T - 1);
-        const float alpha = live ? __uint_as_float(q[NV_R_ALPHA * NT]) : 0.0f, Tr = live ? __uint_as_float(q[NV_R_TR * NT]) : 0.0f;
+        const float ex = live ? __uint_as_float(q[NV_R_EX * NT]) : 1.0f, Tr = live ? __uint_as_float(q[NV_R_TR * NT]) : 0.0f;
+        const float alpha = 1.0f - ex;                                   // the forward's own alpha
         const float rgb[3] = {__uint_as_float(q[NV_R_RGB * NT]), __uint_as_float(q[(NV_R_RGB + 1) * NT]), __uint_as_float(q[(NV_R_RGB + 2) * NT])};
         const float w = alpha * Tr;
         const bool masked = live && w > 1e-4f;
@@ -415,9 +419,10 @@ __global__ __launch_bounds__(NV_BLOCK) void k_nav_run_bwd(nav_params P, nav_run 
         const float S = behind + rs;                                     // sum over k > i of A_k w_k
         suffix += chunk_total;
         // w_i = alpha_i T_i, T_k (k > i) carries the factor (1 - alpha_i + eps):
-        //   d L / d alpha_i = A_i T_i - S_i / (1 - alpha_i + eps);   d alpha_i / d sigma_i = delta_i scale (1 - alpha_i)
+        //   d L / d alpha_i = A_i T_i - S_i / (1 - alpha_i + eps);   d alpha_i / d sigma_i = delta_i scale exp(-delta_i scale sigma_i)
+        // S_i / keep_i with the forward's own (rounded) keep: every T behind i carries that factor, so the quotient does not see its rounding
         const float keep = 1.0f - alpha + 1e-15f;
-        const float gsigma = live ? s.znext_minus_z * P.density_scale * (1.0f - alpha) * (A * Tr - S / keep) : 0.0f;
+        const float gsigma = live ? s.znext_minus_z * P.density_scale * ex * (A * Tr - S / keep) : 0.0f;
 
         float gout[16];
         #pragma unroll

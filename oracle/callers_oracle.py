@@ -58,26 +58,57 @@ def _grid_index(loc, hashmap_size, resolution, gridtype, align_corners):
     return index % hashmap_size
 
 
-def grid_encode(x, embeddings, offsets, per_level_scale, base_resolution=16, bound=1.0, gridtype=0, align_corners=False):
-    """GridEncoder.forward (grid.py:140-156): x [B,3] world coordinates in [-bound, bound] -> [B, L*C] in the dtype of `embeddings`
-    (float32 or float64).  Differentiable w.r.t. x and embeddings."""
-    dt = embeddings.dtype
+def _pinned(v32, v):
+    """Straight-through pin: the VALUE of `v32` (computed in float32) in the dtype of `v`, the GRADIENT path of `v`."""
+    return v32.to(v.dtype) + (v - v.detach())
+
+
+def grid_cells(x, dtype, num_levels, per_level_scale, base_resolution=16, bound=1.0, align_corners=False, pin_float32=False):
+    """Where the encoder puts x [B,3]: (oob [B,1] bool, [(cell [B,3] int64, frac [B,3] in `dtype`) per level]).  frac is differentiable w.r.t. x.
+    pin_float32 (dtype float64 only): every value that SELECTS something -- x01 and its out-of-box test, pos, floor(pos), frac -- is computed in
+    float32 exactly as the float32 path computes it and cast up; the gradient of frac w.r.t. x stays in float64 (d frac / d x = scale / (2 bound))."""
+    dt = dtype
+    pin = bool(pin_float32) and dt == torch.float64
     # grid.py:144 `(inputs + bound) / (2 * bound)` as the reference evaluates it on its GPU: torch divides a tensor by a host scalar by multiplying
     # with the scalar's reciprocal in the tensor's dtype (ATen BinaryDivTrueKernel.cu).  Exact for a power-of-two 2 * bound.
     x01 = (x.to(dt) + bound) * torch.tensor(1.0, dtype=dt).div(torch.tensor(2 * bound, dtype=dt))
-    B, D = x01.shape
-    L = len(offsets) - 1
+    if pin:
+        f32 = torch.float32
+        x01_32 = (x.detach().to(f32) + bound) * torch.tensor(1.0, dtype=f32).div(torch.tensor(2 * bound, dtype=f32))
+        x01 = _pinned(x01_32, x.to(dt) * (1.0 / (2 * bound)))
     S = np.float32(np.log2(per_level_scale))                          # grid.py:33: narrowed to float at the boundary
     oob = ((x01 < 0) | (x01 > 1)).any(dim=-1, keepdim=True)           # gridencoder.cu:100-123
-    scales, resolutions = O.grid_level_table(L, S, base_resolution)   # :125-127 in float32 with libm's exp2f, as the C restatement
+    scales, _ = O.grid_level_table(num_levels, S, base_resolution)    # :125-127 in float32 with libm's exp2f, as the C restatement
+    levels = []
+    for level in range(num_levels):
+        scale = scales[level]
+        if pin:
+            pos32 = x01_32 * float(scale) + (0.0 if align_corners else 0.5)
+            cell = torch.floor(pos32)
+            frac = _pinned(pos32 - cell, x01 * float(scale))
+        else:
+            pos = x01 * float(scale) + (0.0 if align_corners else 0.5)
+            cell = torch.floor(pos.detach())
+            frac = pos - cell
+        levels.append((cell.long().clamp(min=0), frac))               # oob rows are zeroed by the caller; keep their indices in range
+    return oob, levels
+
+
+def grid_encode(x, embeddings, offsets, per_level_scale, base_resolution=16, bound=1.0, gridtype=0, align_corners=False, pin_float32=False):
+    """GridEncoder.forward (grid.py:140-156): x [B,3] world coordinates in [-bound, bound] -> [B, L*C] in the dtype of `embeddings`
+    (float32 or float64).  Differentiable w.r.t. x and embeddings.
+    pin_float32 (float64 tables only): the interpolation, and everything downstream of it, is float64 arithmetic on the float32 path's own cells
+    and fractions (see grid_cells)."""
+    dt = embeddings.dtype
+    B, D = x.shape
+    L = len(offsets) - 1
+    _, resolutions = O.grid_level_table(L, np.float32(np.log2(per_level_scale)), base_resolution)
+    oob, levels = grid_cells(x, dt, L, per_level_scale, base_resolution, bound, align_corners, pin_float32)
     outs = []
     for level in range(L):
         size = int(offsets[level + 1] - offsets[level])
-        scale, resolution = scales[level], int(resolutions[level])
-        pos = x01 * float(scale) + (0.0 if align_corners else 0.5)
-        cell = torch.floor(pos.detach())
-        frac = pos - cell
-        cell = cell.long().clamp(min=0)                               # oob rows are zeroed below; keep their indices in range
+        resolution = int(resolutions[level])
+        cell, frac = levels[level]
         acc = torch.zeros(B, embeddings.shape[1], dtype=dt)
         for corner in range(1 << D):
             w = torch.ones(B, dtype=dt)
@@ -134,9 +165,9 @@ class _GridEncodeFirstOrder(torch.autograd.Function):
     (nav/estimator_helpers.py:384) therefore sees the encoder as a function whose gradient is a constant.  Values = `grid_encode`."""
 
     @staticmethod
-    def forward(ctx, x, embeddings, offsets, per_level_scale, base_resolution, bound, gridtype, align_corners):
+    def forward(ctx, x, embeddings, offsets, per_level_scale, base_resolution, bound, gridtype, align_corners, pin_float32=False):
         ctx.save_for_backward(x, embeddings)
-        ctx.args = (offsets, per_level_scale, base_resolution, bound, gridtype, align_corners)
+        ctx.args = (offsets, per_level_scale, base_resolution, bound, gridtype, align_corners, pin_float32)
         return grid_encode(x.detach(), embeddings.detach(), *ctx.args)
 
     @staticmethod
@@ -153,12 +184,12 @@ class _GridEncodeFirstOrder(torch.autograd.Function):
             if need[k]:
                 g = got.pop(0)
                 out[k] = (torch.zeros_like((x, emb)[k]) if g is None else g).detach()
-        return (out[0], out[1]) + (None,) * 6
+        return (out[0], out[1]) + (None,) * 7
 
 
-def grid_encode_first_order(x, embeddings, offsets, per_level_scale, base_resolution=16, bound=1.0, gridtype=0, align_corners=False):
+def grid_encode_first_order(x, embeddings, offsets, per_level_scale, base_resolution=16, bound=1.0, gridtype=0, align_corners=False, pin_float32=False):
     """`grid_encode` as the reference's autograd.Function differentiates it: first derivatives only, graph-less (see _GridEncodeFirstOrder)"""
-    return _GridEncodeFirstOrder.apply(x, embeddings, offsets, per_level_scale, base_resolution, bound, gridtype, align_corners)
+    return _GridEncodeFirstOrder.apply(x, embeddings, offsets, per_level_scale, base_resolution, bound, gridtype, align_corners, pin_float32)
 
 
 class _SHEncodeFirstOrder(torch.autograd.Function):
@@ -209,12 +240,14 @@ class DefaultField:
     no biases (:45,66).  Parameters are plain leaf tensors so tests read their .grad."""
 
     def __init__(self, embeddings, offsets, per_level_scale, sigma_weights, color_weights, bound, dtype=torch.float32, ff_layout=False,
-                 first_order_encoders=False):
+                 first_order_encoders=False, pin_float32=False):
         """ff_layout: the FFMLP variant of nerf/network_ff.py:51-77 -- colour input cat(SH16, geo15, one zero column) = 32 wide (:67-68),
         colour output 16 wide of which [:3] is used (:72-74); any number of hidden layers in either net.
         first_order_encoders: differentiate the encoders like the reference's autograd.Functions (graph-less gradients, N3) -- needed whenever a
-        caller asks for second derivatives (the pose filter's Hessian); first derivatives are the same either way."""
+        caller asks for second derivatives (the pose filter's Hessian); first derivatives are the same either way.
+        pin_float32: handed to the grid encoder (see grid_encode); changes nothing unless dtype is float64."""
         self.ff_layout = ff_layout
+        self.pin_float32 = bool(pin_float32)
         self._grid = grid_encode_first_order if first_order_encoders else grid_encode
         self._sh = sh_encode_first_order if first_order_encoders else sh_encode
         as_t = lambda a: torch.as_tensor(np.asarray(a), dtype=dtype).clone().requires_grad_(True)        # noqa: E731
@@ -238,7 +271,8 @@ class DefaultField:
         return h
 
     def density(self, x):                                               # network.py:125-143
-        h = self._mlp(self.sigma_weights, self._grid(x, self.embeddings, self.offsets, self.per_level_scale, bound=self.bound))
+        h = self._mlp(self.sigma_weights, self._grid(x, self.embeddings, self.offsets, self.per_level_scale, bound=self.bound,
+                                                         pin_float32=self.pin_float32))
         return {"sigma": trunc_exp(h[..., 0]), "geo_feat": h[..., 1:]}
 
     def color(self, x, d, mask=None, geo_feat=None, **kwargs):          # network.py:163-191
@@ -305,10 +339,16 @@ def _weights(z_vals, sample_dist, sigma, density_scale):
 
 
 def run(field, rays_o, rays_d, bound, num_steps=128, upsample_steps=0, bg_color=1.0, min_near=0.2, density_scale=1.0, training=False,
-        perturb_u=None, pdf_u=None):
+        perturb_u=None, pdf_u=None, pin_float32=False):
     """NeRFRenderer.run (nerf/renderer.py:125-254).  rays_* torch [N,3] (may require grad).  perturb_u: the uniforms of :153 or None.
+    bg_color: a scalar, or three values (one per channel).
+    pin_float32 (upsample_steps = 0, no perturbation): nears, fars, z_vals, sample_dist and the unclipped sample positions take the values the
+    float32 run computes, with the gradient path of this run's dtype (`_pinned`); the clip stays torch's (half the gradient on a tie).  Give the
+    field pin_float32 too: then a float64 run evaluates the float32 run's own samples, cells and fractions.
     Returns dict(image [N,3], depth [N], weights_sum [N], weights [N,T], mask [N,T])."""
     dt = rays_o.dtype
+    if not isinstance(bg_color, (int, float)):
+        bg_color = torch.as_tensor(np.asarray(bg_color, np.float32)).to(dt)
     N = rays_o.shape[0]
     aabb = torch.tensor([-bound] * 3 + [bound] * 3, dtype=dt)
     n, f = O.near_far_from_aabb(rays_o.detach().numpy().astype(np.float32), rays_d.detach().numpy().astype(np.float32),
@@ -319,7 +359,18 @@ def run(field, rays_o, rays_d, bound, num_steps=128, upsample_steps=0, bg_color=
     sample_dist = (fars - nears) / num_steps
     if perturb_u is not None:
         z_vals = z_vals + (perturb_u - 0.5) * sample_dist
+    if pin_float32:
+        if perturb_u is not None or upsample_steps > 0:
+            raise ValueError("pin_float32 restates the fixed-step run: no perturbation, no upsampling")
+        f32 = torch.float32
+        n32, f32s = torch.from_numpy(n).unsqueeze(-1), torch.from_numpy(f).unsqueeze(-1)
+        z32 = n32 + (f32s - n32) * torch.linspace(0.0, 1.0, num_steps, dtype=f32).unsqueeze(0).expand(N, num_steps)
+        z_vals = z32.to(dt)                                             # near / far carry no gradient (:140-141), so neither does z
+        sample_dist = ((f32s - n32) / num_steps).to(dt)
+        xyzs32 = rays_o.detach().to(f32).unsqueeze(-2) + rays_d.detach().to(f32).unsqueeze(-2) * z32.unsqueeze(-1)
     xyzs = rays_o.unsqueeze(-2) + rays_d.unsqueeze(-2) * z_vals.unsqueeze(-1)
+    if pin_float32:
+        xyzs = _pinned(xyzs32, xyzs)
     xyzs = torch.min(torch.max(xyzs, aabb[:3]), aabb[3:])
     dens = {k: v.view(N, num_steps, -1) for k, v in field.density(xyzs.reshape(-1, 3)).items()}
 
@@ -349,6 +400,25 @@ def run(field, rays_o, rays_d, bound, num_steps=128, upsample_steps=0, bg_color=
     image = torch.sum(weights.unsqueeze(-1) * rgbs, dim=-2)
     image = image + (1 - weights_sum).unsqueeze(-1) * bg_color
     return {"image": image, "depth": depth, "weights_sum": weights_sum, "weights": weights, "mask": mask}
+
+
+def rotate_points_float32(x, rot):
+    """p = x @ rot in float32 in the written order of csrc/nav_field.hip's k_nav_density_vj: (x m[0][k] + y m[1][k]) + z m[2][k], one rounding
+    per operation, nothing fused.  x [M,3], rot [3,3] (anything numpy reads) -> float32 numpy [M,3]."""
+    x, m = np.asarray(x, np.float32), np.asarray(rot, np.float32)
+    return np.stack([(x[:, 0] * m[0, k] + x[:, 1] * m[1, k]) + x[:, 2] * m[2, k] for k in range(3)], axis=-1).astype(np.float32)
+
+
+def point_query(field, x, rot=None, pin_float32=False):
+    """The planner's query (simulate.py:340-343): field.density(x @ rot) for x [M,3] (may require grad), rot a 3x3 matrix or None.
+    pin_float32: the rotated point takes the float32 values of `rotate_points_float32`, with the gradient path of x @ rot in the field's dtype.
+    Returns the field's dict (sigma [M], geo_feat [M,15])."""
+    p = x.to(field.dtype)
+    if rot is not None:
+        p = p @ torch.as_tensor(np.asarray(rot, np.float32)).to(field.dtype)
+        if pin_float32:
+            p = _pinned(torch.from_numpy(rotate_points_float32(x.detach().numpy(), rot)), p)
+    return field.density(p)
 
 
 # ------------------------------------------------------------------------------------------------------------------------
