@@ -642,6 +642,47 @@ int ngp_plan_epochs(const ngp_nav_field_t* field_host, const void* prepared, con
                     uint32_t first_epoch, uint32_t n_epochs, int update, float* losses, float* per_state,
                     void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------ */
+/* Pose filter  (reference: Estimator.estimate_relative_pose / measurement_fn, */
+/* nav/estimator_helpers.py:173-327; csrc/nav_filter.hip, DESIGN.md §3.5 "Native pose filter") */
+/* ------------------------------------------------------------------------ */
+
+/* Host struct.  The state is the filter's 12-vector (position, velocity, rotation vector, rate); the camera pose follows from state[0:3] and
+ * state[6:9] as in measurement_fn.  1 <= B <= 2^20 rays per iteration, num_steps as for ngp_nav_run_forward (1 .. 4096). */
+typedef struct {
+    uint32_t H, W;               /* image size */
+    float intrinsics[4];         /* fx, fy, cx, cy */
+    float aabb[6];
+    float min_near;
+    uint32_t num_steps;          /* samples per ray */
+    float bg[3];                 /* background colour */
+    uint32_t B;                  /* rays per iteration */
+    float start_state[12];       /* the Mahalanobis centre */
+    float sig_inv[144];          /* inverse covariance, row-major */
+    double lr, beta1, beta2, eps; /* torch.optim.Adam; rounded to float32 as torch does */
+} ngp_filter_cfg_t;
+
+/* Adam state, device float32: exp_avg [12], exp_avg_sq [12], grad [12] (the gradient of the last iteration), step [1]; zero it to restart. */
+#define NGP_FILTER_ADAM_FLOATS 37u
+
+/* bytes of the workspace of ngp_filter_iterations: rays_o, rays_d [B,3], nears, fars [B], image [B,3], depth, weights_sum [B], grad_image [B,3],
+ * the run kernels' saved record (ngp_nav_run_saved_bytes(B, num_steps)), grad_rays_o, grad_rays_d [B,3], the loss partials; 0 outside the supported
+ * B, num_steps */
+size_t ngp_filter_workspace(uint32_t B, uint32_t num_steps);
+/* n_iter iterations of the filter's loop: per iteration the rays of the batch from the state, ngp_nav_run_forward, the loss, ngp_nav_run_backward and the
+ * step, 5 launches on `stream`, no synchronisation, no host read.  state [12] is updated in place.  target [H,W,3] f32; batches [*,B,2] i32 (row, col)
+ * pairs, iteration k uses slice first_iter + k (an index outside the image is clamped into it; checking is the caller's).  losses [n_iter], states_out
+ * [n_iter,12], grads_out [n_iter,12] (each may be NULL): loss, state and gradient BEFORE the iteration's step.
+ * update = 1: Adam step on state in place; update = 0: loss and gradient only (adam_state's grad slot), state and moments untouched.
+ * Deterministic: two runs are bit-identical.  Every refusal (the field's included) happens on the host before anything reaches the device. */
+int ngp_filter_iterations(const ngp_nav_field_t* field_host, const void* prepared, const ngp_filter_cfg_t* cfg_host, float* state, float* adam_state,
+                          const float* target, const int32_t* batches, uint32_t first_iter, uint32_t n_iter, int update, float* losses,
+                          float* states_out, float* grads_out, void* workspace, size_t workspace_bytes, void* stream);
+/* The first of those launches alone: the rays an iteration renders for `state` and one batch [B,2] -- rays_o, rays_d [B,3], nears, fars [B], bit for bit.
+ * Reads H, W, intrinsics, aabb, min_near and B of cfg_host. */
+int ngp_filter_rays(const ngp_filter_cfg_t* cfg_host, const float* state, const int32_t* batch, float* rays_o, float* rays_d, float* nears,
+                    float* fars, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -606,3 +606,262 @@ class NativePlanner:
                "total_cost": res["per_state"].cpu().tolist()}
         with open(filename, "w+") as f:
             json.dump(out, f, indent=4)
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# the pose filter's optimisation loop on the device (csrc/nav_filter.hip): five launches per iteration, no host synchronisation
+# ------------------------------------------------------------------------------------------------------------------------
+def _hat(v):
+    """skew_matrix (nav/math_utils.py:176-185)"""
+    S = torch.zeros(3, 3, dtype=v.dtype, device=v.device)
+    S[0, 1], S[0, 2] = -v[2], v[1]
+    S[1, 0], S[1, 2] = v[2], -v[0]
+    S[2, 0], S[2, 1] = -v[1], v[0]
+    return S
+
+
+def _measurement_pose(state):
+    """measurement_fn's pose chain (nav/estimator_helpers.py:301-309) in torch: vec_to_rot_matrix with its `1e-10 + angle` guard, rot_x(pi/2),
+    nerf_matrix_to_ngp_torch -> [4,4] camera-to-world"""
+    kw = dict(dtype=torch.float32, device=state.device)
+    angle = torch.norm(state[6:9], dim=-1, keepdim=True)
+    K = _hat(state[6:9] / (1e-10 + angle))
+    R = torch.eye(3, **kw) + torch.sin(angle) * K + (1 - torch.cos(angle)) * K @ K
+    phi = torch.tensor(torch.pi / 2)
+    about_x = torch.tensor([[1., 0., 0.], [0., torch.cos(phi), -torch.sin(phi)], [0., torch.sin(phi), torch.cos(phi)]], **kw)
+    neg_yz = torch.tensor([[1, 0, 0], [0, -1, 0], [0, 0, -1]], **kw)
+    flip_yz = torch.tensor([[0, 1, 0], [0, 0, 1], [1, 0, 0]], **kw)
+    pose = torch.eye(4, **kw)
+    pose[:3, :3] = flip_yz @ (about_x @ R) @ neg_yz
+    pose[:3, 3] = flip_yz @ state[:3]
+    return pose
+
+
+def nearest_pd(A):
+    """The nearest positive-definite matrix in the Frobenius norm (N. J. Higham, "Computing a nearest symmetric positive semidefinite matrix", 1988),
+    as Estimator.estimate_state uses it (nav/math_utils.py:40-86): the symmetric part B of A, averaged with its polar factor H (from the SVD of B),
+    symmetrised; while Cholesky still refuses the result, the diagonal is lifted by multiples of its smallest eigenvalue plus one spacing of |A|.
+    numpy, float64 throughout -- except that spacing, which is float32's: the filter's Hessian is float32 and the covariance goes back into float32
+    kernels, and a margin of one float64 spacing (1e-16) leaves a matrix whose inverse cannot be inverted back even in float64."""
+    import numpy as np
+
+    def is_pd(M):
+        try:
+            np.linalg.cholesky(M)
+            return True
+        except np.linalg.LinAlgError:
+            return False
+
+    A = np.asarray(A, np.float64)
+    B = (A + A.T) / 2
+    _, s, Vt = np.linalg.svd(B)
+    H = Vt.T @ (np.diag(s) @ Vt)
+    P = (B + H) / 2
+    P = (P + P.T) / 2
+    spacing = float(np.spacing(np.float32(np.linalg.norm(A))))
+    eye = np.eye(A.shape[0])
+    k = 1
+    while not is_pd(P):
+        lowest = np.min(np.real(np.linalg.eigvals(P)))
+        P = P + eye * (-lowest * k ** 2 + spacing)
+        k += 1
+    return P
+
+
+class NativePoseFilter:
+    """Estimator (nav/estimator_helpers.py) with its optimisation loop native: measurement_fn -> backward -> Adam run as ngp_filter_iterations, i.e. per
+    iteration one launch for the batch's rays from the state, NativeNavQueries' run kernel forward, one launch for the loss, the run kernel backward
+    and one launch for the chain back to the state, the Mahalanobis term and the Adam step.  `filter_cfg` takes the reference's keys batch_size,
+    lrate, N_iter, sig0, Q.  The feature detector, its dilation and the agent's dynamics stay with the caller, who hands over `interest_regions`
+    ([M,2] (row, col) pairs) or ready batches; loss, state and gradient histories are device tensors.
+
+        filt = NativePoseFilter(filter_cfg, queries, start_state)          # queries: NativeNavQueries
+        batches = filt.draw_batches(interest_regions, filt.iter, rng)
+        xt = filt.estimate_relative_pose(target, xt_propagated, sig_propagated, batches)
+    """
+
+    def __init__(self, filter_cfg, queries, start_state=None):
+        if not isinstance(queries, NativeNavQueries):
+            raise ValueError(f"NativePoseFilter needs a NativeNavQueries (the fused float32 queries), got {type(queries).__name__}")
+        self.queries = queries
+        self.device = queries.native.field.encoder.embeddings.device
+        self.cfg = filter_cfg
+        self.batch_size, self.lrate, self.iter = int(filter_cfg["batch_size"]), float(filter_cfg["lrate"]), int(filter_cfg["N_iter"])
+        self.sig, self.Q = filter_cfg["sig0"], filter_cfg["Q"]
+        self.xt = start_state
+        self.losses = self.states = self.grads = None
+        self.target = self.batch = None
+        self.sig_inv = None                                  # the float32 inverse covariance of the last call, [12,12] on the host
+        self._ws = None
+
+    # -- plumbing ------------------------------------------------------------------------------------------------------
+    def _vec(self, v):
+        return torch.as_tensor(v).detach().to(self.device, torch.float32).reshape(12)
+
+    def _target(self, target):
+        q = self.queries
+        if not (isinstance(target, torch.Tensor) and target.is_cuda and target.dtype == torch.float32 and tuple(target.shape) == (q.H, q.W, 3)):
+            raise ValueError(f"target must be a float32 [{q.H}, {q.W}, 3] tensor on the GPU")
+        return target.contiguous()
+
+    def _batches(self, batches, check=True):
+        """[n,B,2] (or one batch [B,2]) (row, col) pairs -> int32, contiguous, on the device; `check` reads their range back (one synchronisation)"""
+        b = torch.as_tensor(batches)
+        if b.dim() == 2:
+            b = b[None]
+        if b.dim() != 3 or b.shape[2] != 2 or b.shape[1] < 1 or b.dtype in (torch.float16, torch.float32, torch.float64, torch.bool):
+            raise ValueError("batches must be integer (row, col) pairs of shape [n, B, 2]")
+        if check and b.numel():
+            lo, rmax, cmax = int(b.min()), int(b[..., 0].max()), int(b[..., 1].max())
+            if lo < 0 or rmax >= self.queries.H or cmax >= self.queries.W:
+                raise ValueError(f"batches hold a pixel outside the {self.queries.H} x {self.queries.W} image")
+        return b.to(self.device, torch.int32).contiguous()
+
+    def _cfg_struct(self, B, start_state=None, sig=None):
+        """the host struct of the C calls; without start_state / sig only the view (what ngp_filter_rays reads)"""
+        import ngp_hip as _hip
+        q = self.queries
+        ren = q.renderer
+        c = _hip.ngp_filter_cfg_t()
+        c.H, c.W, c.num_steps, c.B = int(q.H), int(q.W), int(q.num_steps), int(B)
+        c.intrinsics[:] = [float(v) for v in q.intrinsics]
+        c.aabb[:] = [float(v) for v in ren._aabb().tolist()]
+        c.min_near = float(ren.min_near)
+        c.bg[:] = [1.0, 1.0, 1.0]                            # render_fn's bg_color = 1 (simulate.py:345)
+        if start_state is None:
+            return c
+        c.start_state[:] = [float(v) for v in self._vec(start_state).cpu().tolist()]
+        # mahalanobis() inverts the covariance in every iteration (nav/math_utils.py:22-24): the same matrix every time, inverted once here
+        self.sig_inv = torch.inverse(torch.as_tensor(sig).detach().to(self.device, torch.float32)).cpu()
+        c.sig_inv[:] = [float(v) for v in self.sig_inv.reshape(-1).tolist()]
+        c.lr, c.beta1, c.beta2, c.eps = self.lrate, 0.9, 0.999, 1e-8
+        return c
+
+    def _workspace(self, B):
+        import ngp_hip as _hip
+        nbytes = _hip.lib().ngp_filter_workspace(int(B), int(self.queries.num_steps))
+        if self._ws is None or self._ws.numel() < nbytes:
+            self._ws = _hip.workspace(nbytes, self.device)
+        return self._ws
+
+    def new_adam_state(self):
+        """zeroed Adam moments and step: the reference builds a new optimiser in every estimate_relative_pose"""
+        import ngp_hip as _hip
+        return torch.zeros(_hip.FILTER_ADAM_FLOATS, dtype=torch.float32, device=self.device)
+
+    def run_iterations(self, first_iter, n_iter, adam_state, state, start_state, sig, target, batches, update=True, losses=None, states=None,
+                       grads=None):
+        """queue n_iter iterations (5 launches each) on the current stream; no synchronisation on the device side (the covariance is inverted
+        once, on the way in).  state: [12] float32 device tensor, updated in place; batches: [n,B,2] int32 device tensor from draw_batches, iteration
+        k uses batches[first_iter + k]; losses [n_iter], states, grads [n_iter,12]: device tensors or None, the values before each step"""
+        import ctypes
+        import ngp_hip as _hip
+        if not (batches.is_cuda and batches.dtype == torch.int32 and batches.is_contiguous() and batches.dim() == 3 and batches.shape[2] == 2):
+            raise ValueError("run_iterations takes batches as draw_batches returns them: [n, B, 2] int32 on the GPU")
+        if int(first_iter) < 0 or int(first_iter) + int(n_iter) > batches.shape[0]:
+            raise ValueError(f"iterations {first_iter} .. {int(first_iter) + int(n_iter)} reach past the {batches.shape[0]} batches")
+        if not (state.is_cuda and state.dtype == torch.float32 and state.is_contiguous() and state.numel() == 12):
+            raise ValueError("state must be a contiguous float32 [12] tensor on the GPU")
+        for name, t, shape in (("losses", losses, (n_iter,)), ("states", states, (n_iter, 12)), ("grads", grads, (n_iter, 12))):
+            if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape):
+                raise ValueError(f"{name} must be a contiguous float32 {list(shape)} tensor on the GPU")
+        B = int(batches.shape[1])
+        target = self._target(target)
+        st, prep = self.queries.native.struct()
+        c = self._cfg_struct(B, start_state, sig)
+        ws = self._workspace(B)
+        _hip.check(_hip.lib().ngp_filter_iterations(ctypes.byref(st), _hip.ptr(prep), ctypes.byref(c), _hip.ptr(state), _hip.ptr(adam_state),
+                                                    _hip.ptr(target), _hip.ptr(batches), int(first_iter), int(n_iter), 1 if update else 0,
+                                                    _hip.ptr(losses), _hip.ptr(states), _hip.ptr(grads), _hip.ptr(ws), ws.numel(), _hip.stream()),
+                   "filter_iterations")
+
+    def rays(self, state, batch):
+        """the rays an iteration renders at `state` for one batch [B,2] of (row, col) pairs, bit for bit (the loop's first launch alone):
+        dict(rays_o, rays_d [B,3], nears, fars [B]).  The pose chain and ngp_get_rays' arithmetic run in float32 in the order csrc/nav_filter.hip
+        and csrc/ngp_camera.h write them, so they equal torch's get_rays to about an ulp, not bit for bit."""
+        import ctypes
+        import ngp_hip as _hip
+        batch = self._batches(batch)[0]
+        B = int(batch.shape[0])
+        kw = dict(dtype=torch.float32, device=self.device)
+        out = dict(rays_o=torch.empty(B, 3, **kw), rays_d=torch.empty(B, 3, **kw), nears=torch.empty(B, **kw), fars=torch.empty(B, **kw))
+        c = self._cfg_struct(B)
+        _hip.check(_hip.lib().ngp_filter_rays(ctypes.byref(c), _hip.ptr(self._vec(state).contiguous()), _hip.ptr(batch), _hip.ptr(out["rays_o"]),
+                                              _hip.ptr(out["rays_d"]), _hip.ptr(out["nears"]), _hip.ptr(out["fars"]), _hip.stream()), "filter_rays")
+        return out
+
+    # -- the reference's interface ---------------------------------------------------------------------------------------
+    def draw_batches(self, interest_regions, n_iter, rng):
+        """the batches of n_iter iterations, drawn before the loop: iteration k is interest_regions[rng.choice(M, size=batch_size, replace=False)]
+        (nav/estimator_helpers.py:229-230 with an explicit numpy Generator) -> [n_iter, batch_size, 2] int32 on the device"""
+        import numpy as np
+        regions = np.asarray(interest_regions)
+        if regions.ndim != 2 or regions.shape[1] != 2 or not np.issubdtype(regions.dtype, np.integer):
+            raise ValueError("interest_regions must be integer (row, col) pairs of shape [M, 2]")
+        M, B = regions.shape[0], self.batch_size
+        if M < B:
+            raise ValueError(f"{M} interest points cannot fill a batch of {B} without replacement")
+        q = self.queries
+        if M and (regions.min() < 0 or regions[:, 0].max() >= q.H or regions[:, 1].max() >= q.W):
+            raise ValueError(f"interest_regions hold a pixel outside the {q.H} x {q.W} image")
+        out = np.empty((int(n_iter), B, 2), np.int32)
+        for k in range(int(n_iter)):
+            out[k] = regions[rng.choice(M, size=B, replace=False)]
+        return torch.from_numpy(out).to(self.device)
+
+    def cost_and_gradient(self, state, start_state, sig, target, batch):
+        """measurement_fn(state, start_state, sig, target, batch) and its gradient: dict(loss, rgb_loss, grad [12]), device tensors"""
+        batches = self._batches(batch)
+        adam = self.new_adam_state()
+        loss = torch.empty(1, dtype=torch.float32, device=self.device)
+        x = self._vec(state).clone()
+        self.run_iterations(0, 1, adam, x, start_state, sig, target, batches, update=False, losses=loss)
+        delta = (x - self._vec(start_state)).double().cpu()
+        process = delta @ self.sig_inv.double() @ delta
+        return dict(loss=loss[0], rgb_loss=loss[0] - process.to(self.device, torch.float32), grad=adam[24:36])
+
+    def estimate_relative_pose(self, target, start_state, sig, batches):
+        """Estimator.estimate_relative_pose's loop (nav/estimator_helpers.py:207-291): N_iter Adam iterations from start_state + 1e-6 with fresh
+        moments, all queued in one call.  Keeps losses [N_iter], states and grads [N_iter,12] (before each step), target and the last batch."""
+        n = self.iter
+        batches = self._batches(batches)
+        if batches.shape[0] < n:
+            raise ValueError(f"{n} iterations need {n} batches, got {batches.shape[0]}")
+        target = self._target(target)
+        state = self._vec(start_state).clone() + 1e-6
+        self.losses = torch.empty(n, dtype=torch.float32, device=self.device)
+        self.states = torch.empty(n, 12, dtype=torch.float32, device=self.device)
+        self.grads = torch.empty(n, 12, dtype=torch.float32, device=self.device)
+        if n:
+            self.run_iterations(0, n, self.new_adam_state(), state, start_state, sig, target, batches, losses=self.losses, states=self.states,
+                                grads=self.grads)
+        self.target = target
+        self.batch = batches[n - 1] if n else None
+        return state.detach()
+
+    def measurement_fn(self, state, start_state, sig, target, batch):
+        """Estimator.measurement_fn (nav/estimator_helpers.py:293-327) in torch over the queries (differentiable; the Hessian's route)"""
+        delta = state - start_state
+        process = delta @ torch.inverse(sig) @ delta
+        H, W, _ = target.shape
+        rays = self.queries.get_rays_fn(_measurement_pose(state).reshape(1, 4, 4))
+        rows, cols = batch[:, 0].long(), batch[:, 1].long()
+        rays_o = rays["rays_o"].reshape(H, W, -1)[rows, cols]
+        rays_d = rays["rays_d"].reshape(H, W, -1)[rows, cols]
+        rgb = self.queries.render_fn(rays_o.reshape(1, -1, 3), rays_d.reshape(1, -1, 3))["image"].reshape(-1, 3)
+        return torch.nn.functional.mse_loss(rgb, target[rows, cols]) + process
+
+    def measurement_hessian(self, state, start_state, sig):
+        """the 12 x 12 Hessian estimate_state asks for once per time step (nav/estimator_helpers.py:384), at the target and the last batch of
+        estimate_relative_pose; through torch.autograd.functional.hessian, as in the reference"""
+        if self.target is None or self.batch is None:
+            raise RuntimeError("measurement_hessian needs the target and batch of an estimate_relative_pose call")
+        start, sig = self._vec(start_state), torch.as_tensor(sig).detach().to(self.device, torch.float32)
+        return torch.autograd.functional.hessian(lambda x: self.measurement_fn(x, start, sig, self.target, self.batch), self._vec(state).clone())
+
+    def covariance(self, hessian):
+        """estimate_state's covariance update (nav/estimator_helpers.py:387-394): the inverse of the positive-definite matrix nearest to the Hessian,
+        [12,12] float64 on the host (nearest_pd says why; `.float()` it for the next time step's `sig`)"""
+        import numpy as np
+        h = hessian.detach().cpu().numpy() if isinstance(hessian, torch.Tensor) else np.asarray(hessian)
+        return torch.inverse(torch.from_numpy(nearest_pd(h)))

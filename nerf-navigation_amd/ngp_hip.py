@@ -134,6 +134,9 @@ _SIGNATURES = {
     "ngp_plan_workspace": (c_sz, [c_u32, c_u32]),
     "ngp_plan_kinematics": (c_int, [c_vp, c_vp, c_vp, c_u32, c_vp, c_u32, c_vp, c_vp, c_vp, c_vp]),
     "ngp_plan_epochs": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_u32, c_u32, c_u32, c_u32, c_int, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "ngp_filter_workspace": (c_sz, [c_u32, c_u32]),
+    "ngp_filter_iterations": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_u32, c_u32, c_int, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "ngp_filter_rays": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
 }
 
 EXPORTS = tuple(_SIGNATURES)
@@ -177,6 +180,16 @@ class ngp_plan_cfg_t(ctypes.Structure):
 def plan_adam_floats(R):
     """include/ngp_hip.h: NGP_PLAN_ADAM_FLOATS(R)"""
     return 3 * (4 * int(R) + 2) + 1
+
+
+class ngp_filter_cfg_t(ctypes.Structure):
+    """include/ngp_hip.h: ngp_filter_cfg_t"""
+    _fields_ = [("H", c_u32), ("W", c_u32), ("intrinsics", c_f32 * 4), ("aabb", c_f32 * 6), ("min_near", c_f32), ("num_steps", c_u32),
+                ("bg", c_f32 * 3), ("B", c_u32), ("start_state", c_f32 * 12), ("sig_inv", c_f32 * 144), ("lr", ctypes.c_double),
+                ("beta1", ctypes.c_double), ("beta2", ctypes.c_double), ("eps", ctypes.c_double)]
+
+
+FILTER_ADAM_FLOATS = 37                                      # include/ngp_hip.h: NGP_FILTER_ADAM_FLOATS
 
 
 def build(verbose=False):
