@@ -527,6 +527,23 @@ int ngp_nav_run_backward(const ngp_nav_field_t* field_host, const void* prepared
                          const float* grad_image, const float* grad_depth, const float* grad_weights_sum, const void* saved, size_t saved_bytes,
                          float* grad_rays_o, float* grad_rays_d, void* stream);
 
+/* Training forward and backward of the same field (NeRFNetwork.forward, nerf/network.py:95-123, float32; csrc/nav_train.hip).
+ * forward: xyzs, dirs [M,3] -> sigmas [M] = exp(h0) (field_host->density_scale is NOT applied: the renderer does that), rgbs [M,3] after the sigmoid;
+ *   a sample outside [-bound, bound]^3 encodes to zeros.  saved: ngp_nav_field_train_saved_bytes(M) bytes (the 32 encoded features, 128 B per sample).
+ * backward: grad_sigmas [M], grad_rgbs [M,3] -> grad_enc f32 [16][M][2] (the `grad` of ngp_grid_encode_backward, dtype float32; may be NULL) and
+ *   grad_weights f32 [9344]: sigma_net.0 [64,32], sigma_net.1 [16,64], color_net.0 [64,31], color_net.1 [64,64], color_net.2 [3,64] back to back
+ *   (may be NULL, but not both; then no workspace is needed).  Both are fully written.  trunc_exp's clamped derivative and the sigmoid's are applied here.
+ *   No float atomics: per-workgroup sums in `workspace` (ngp_nav_field_train_workspace(M) bytes) added in a fixed order: two runs, the same bits.
+ * Nothing flows to xyzs or dirs.  Refusals (the field's as for ngp_nav_field_prepare; null pointers NGP_EINVAL; short `saved` or `workspace`
+ * NGP_EWORKSPACE) happen before anything reaches the device.  M = 0: NGP_OK, nothing queued; both size functions return 0. */
+size_t ngp_nav_field_train_saved_bytes(uint32_t M);
+size_t ngp_nav_field_train_workspace(uint32_t M);
+int ngp_nav_field_train_forward(const ngp_nav_field_t* field_host, const void* prepared, const float* xyzs, const float* dirs, uint32_t M,
+                                float* sigmas, float* rgbs, void* saved, size_t saved_bytes, void* stream);
+int ngp_nav_field_train_backward(const ngp_nav_field_t* field_host, const void* prepared, const void* saved, const float* xyzs, const float* dirs,
+                                 uint32_t M, const float* grad_sigmas, const float* grad_rgbs, float* grad_enc, float* grad_weights,
+                                 void* workspace, size_t workspace_bytes, void* stream);
+
 /* One whole frame of NeRFRenderer.run_cuda's inference branch (nerf/renderer.py:325-374) of the DEFAULT float32 field in one launch
  * (csrc/nav_frame.hip): ngp_render_frame for the model above, float32 throughout.  The semantics are ngp_render_frame's, word for
  * word: one resumable march per ray from `near`, at most max_steps samples per ray, a ray stops after the sample whose incoming T is below 1e-4,

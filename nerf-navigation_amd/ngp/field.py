@@ -146,6 +146,69 @@ class _field_train(Function):
         return None, None, grad_emb, g_ws, g_wc, None
 
 
+class _field_train_f32(Function):
+    """NGPField.forward and its backward in native float32 launches (csrc/nav_train.hip): forward = one launch that keeps the 32 encoded features
+    per sample (128 B); backward = both nets recomputed from them, the activation gradients on the VALU and the five weight gradients on the matrix
+    cores in one launch, a fixed-order sum of the workgroups' partials (no atomics), then the encoder's own float32 table scatter.  Replaces the
+    ~60 launches and ~1.5 KB per sample of the op-by-op graph.  The weight gradients arrive in nn.Linear's own [out, in] layout."""
+
+    @staticmethod
+    def forward(ctx, x, d, embeddings, w_s0, w_s1, w_c0, w_c1, w_c2, field):
+        x, d = x.contiguous(), d.contiguous()
+        M = x.shape[0]
+        L = _hip.lib()
+        st, prep = field._native_field().struct()
+        sig = torch.empty(M, dtype=torch.float32, device=x.device)
+        rgb = torch.empty(M, 3, dtype=torch.float32, device=x.device)
+        saved = _hip.workspace(L.ngp_nav_field_train_saved_bytes(M), x.device)
+        with torch.cuda.device(x.device), _hip.timed("nav_field_train_forward"):
+            _hip.check(L.ngp_nav_field_train_forward(ctypes.byref(st), _hip.ptr(prep), _hip.ptr(x), _hip.ptr(d), M, _hip.ptr(sig), _hip.ptr(rgb),
+                                                     _hip.ptr(saved), saved.numel(), _hip.stream()), "nav_field_train_forward")
+        ctx.save_for_backward(x, d, saved, prep, embeddings)
+        ctx.fstruct, ctx.field = st, field
+        return sig, rgb
+
+    @staticmethod
+    def backward(ctx, g_sig, g_rgb):
+        x, d, saved, prep, embeddings = ctx.saved_tensors
+        field, enc = ctx.field, ctx.field.encoder
+        M = x.shape[0]
+        L = _hip.lib()
+        need_table, need_weights = bool(ctx.needs_input_grad[2]), any(ctx.needs_input_grad[3:8])
+        if M == 0 or not (need_table or need_weights):
+            zeros = lambda i, p: torch.zeros_like(p) if ctx.needs_input_grad[i] else None          # noqa: E731
+            ws = [l.weight for l in list(field.sigma_net) + list(field.color_net)]
+            return (None, None, zeros(2, embeddings)) + tuple(zeros(3 + k, w) for k, w in enumerate(ws)) + (None,)
+        g_sig = torch.zeros(M, dtype=torch.float32, device=x.device) if g_sig is None else g_sig.contiguous().float()
+        g_rgb = torch.zeros(M, 3, dtype=torch.float32, device=x.device) if g_rgb is None else g_rgb.contiguous().float()
+        grad_enc = torch.empty(enc.num_levels, M, enc.level_dim, dtype=torch.float32, device=x.device) if need_table else None
+        g_w = torch.empty(9344, dtype=torch.float32, device=x.device) if need_weights else None
+        work = _hip.workspace(L.ngp_nav_field_train_workspace(M), x.device) if need_weights else None     # per-workgroup partial sums: nothing to clear
+        with torch.cuda.device(x.device):
+            with _hip.timed("nav_field_train_backward"):
+                _hip.check(L.ngp_nav_field_train_backward(ctypes.byref(ctx.fstruct), _hip.ptr(prep), _hip.ptr(saved), _hip.ptr(x), _hip.ptr(d), M,
+                                                          _hip.ptr(g_sig), _hip.ptr(g_rgb), _hip.ptr(grad_enc), _hip.ptr(g_w), _hip.ptr(work),
+                                                          work.numel() if work is not None else 0, _hip.stream()), "nav_field_train_backward")
+            grad_emb = None
+            if need_table:
+                inputs = ((x + field.bound) / (2 * field.bound)).contiguous()          # GridEncoder.forward (gridencoder/grid.py:144)
+                grad_emb = torch.zeros_like(embeddings)
+                dummy = torch.empty(1, dtype=torch.float32, device=x.device)
+                with _hip.timed("grid_encode_backward"):
+                    _hip.check(L.ngp_grid_encode_backward(_hip.ptr(grad_enc), _hip.ptr(inputs), _hip.ptr(embeddings), _hip.ptr(enc.offsets), _hip.ptr(grad_emb),
+                                                          M, 3, enc.level_dim, enc.num_levels, float(np.log2(enc.per_level_scale)), enc.base_resolution, 0,
+                                                          _hip.ptr(dummy), _hip.ptr(dummy), enc.gridtype_id, int(enc.align_corners), _hip.F32, _hip.stream()),
+                               "grid_encode_backward")
+        g_ws = [None] * 5
+        if need_weights:
+            at = 0
+            for k, shape in enumerate(((64, 32), (16, 64), (64, 31), (64, 64), (3, 64))):
+                n = shape[0] * shape[1]
+                g_ws[k] = g_w[at:at + n].view(shape)
+                at += n
+        return (None, None, grad_emb) + tuple(g_ws) + (None,)
+
+
 class _ParamEpoch:
     """Cached derived copies of the parameters (half table, packed weights, the nav kernels' transposes) are keyed on the tensors'
     `_version` counters AND on this epoch.  Not every in-place update bumps `_version` (torch's fused Adam updates parameters without
@@ -392,7 +455,7 @@ class NGPField(_ParamEpoch, nn.Module):
     """nerf/network.py: the same field with nn.Linear(bias=False) layers (32->64->16 ; 31->64->64->3)."""
 
     def __init__(self, bound=1, num_layers=2, hidden_dim=64, geo_feat_dim=15, num_layers_color=3, hidden_dim_color=64,
-                 density_scale=1, bg_radius=-1, num_layers_bg=2, hidden_dim_bg=64):
+                 density_scale=1, bg_radius=-1, num_layers_bg=2, hidden_dim_bg=64, fused_training=False):
         super().__init__()
         self.bound = bound
         self.density_scale = density_scale
@@ -411,6 +474,9 @@ class NGPField(_ParamEpoch, nn.Module):
             self.encoder_bg, self.in_dim_bg = get_encoder("hashgrid", input_dim=2, num_levels=4, log2_hashmap_size=19, desired_resolution=2048)
             dims = [self.in_dim_bg + self.in_dim_dir] + [hidden_dim_bg] * (num_layers_bg - 1) + [3]
             self.bg_net = nn.ModuleList([nn.Linear(dims[i], dims[i + 1], bias=False) for i in range(num_layers_bg)])
+        self.fused_training = bool(fused_training)      # float32 training forwards of the default shape go through _field_train_f32 (off: the op chain)
+        self._native = None                             # ngp.nav._NativeField: the descriptor and the prepared transposes the native kernels read
+        self._native_ok = {}                            # {layout: does the library accept the field}, asked once per layout
         self._watch_parameters()
 
     @staticmethod
@@ -421,8 +487,44 @@ class NGPField(_ParamEpoch, nn.Module):
                 h = F.relu(h, inplace=True)
         return h
 
+    def _apply(self, fn, *args, **kwargs):
+        self._native, self._native_ok = None, {}        # .to() / .cuda(i) replace parameter storage
+        return super()._apply(fn, *args, **kwargs)
+
+    def _native_field(self):
+        """ngp.nav._NativeField of this field (the code NativeNavQueries uses: one ngp_nav_field_prepare per parameter change); raises RuntimeError
+        for a field that has not the default shape"""
+        if self._native is None:
+            import types
+            from ngp import nav
+            # density_scale 1: the training kernels leave it to the renderer (nerf/renderer.py:176 of this tree's ngp/render.py)
+            self._native = nav._NativeField(types.SimpleNamespace(field=self, density_scale=1.0))
+        return self._native
+
+    def _fused_training_applies(self, x, d):
+        if not (self.fused_training and torch.is_grad_enabled() and not torch.is_autocast_enabled() and x.is_cuda and d.is_cuda
+                and x.dtype == torch.float32 and d.dtype == torch.float32 and x.dim() == 2 and d.dim() == 2 and x.shape[0] > 0
+                and not x.requires_grad and not d.requires_grad):
+            return False
+        e = self.encoder
+        layout = (e.offsets.data_ptr(), e.embeddings.data_ptr(), float(self.bound), str(e.embeddings.device))
+        ok = self._native_ok.get(layout)
+        if ok is None:
+            try:
+                self._native_field().struct()           # the shape test of _NativeField.__init__, then the library's own (ngp_nav_field_prepare)
+                ok = True
+            except RuntimeError:
+                ok = False
+            self._native_ok = {layout: ok}
+        if not ok:
+            return False
+        return any(p.requires_grad for p in self._native_field()._params())
+
     def forward(self, x, d):
         self._training_forward()
+        if self.fused_training and self._fused_training_applies(x, d):
+            ws = [l.weight for l in list(self.sigma_net) + list(self.color_net)]
+            return _field_train_f32.apply(x, d, self.encoder.embeddings, *ws, self)
         h = self._mlp(self.sigma_net, self.encoder(x, bound=self.bound))
         sigma = trunc_exp(h[..., 0])
         geo_feat = h[..., 1:]
