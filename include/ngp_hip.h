@@ -700,6 +700,27 @@ int ngp_filter_iterations(const ngp_nav_field_t* field_host, const void* prepare
 int ngp_filter_rays(const ngp_filter_cfg_t* cfg_host, const float* state, const int32_t* batch, float* rays_o, float* rays_d, float* nears,
                     float* fars, void* stream);
 
+/* The rest of the estimator's time step (Estimator.estimate_state, nav/estimator_helpers.py:347-406; DESIGN.md §3.5 "Native time step").  Both entry points
+ * evaluate the reference's formulas as written in float64 from the float32 inputs and round every output once. */
+typedef struct { float dt, mass, g; float I[9]; } ngp_filter_dyn_t;   /* Agent's cfg (agent_helpers.py:56-61); I row-major */
+
+/* drone_dynamics, its Jacobian and the covariance propagation: ONE launch, one workgroup, no synchronisation.
+ * state [12], action [4] (thrust, torque), sig, Q [12,12]: device float32.
+ * next_state [12]; A [12,12] (may be NULL); sig_prop [12,12] = (A sig) A^T + Q (may be NULL; needs sig and Q).
+ * Refused on the host: null pointers, dt or mass not finite or <= 0, an I whose determinant (in double) is 0 or not finite; I is inverted in double
+ * on the host (adjugate). */
+int ngp_filter_propagate(const ngp_filter_dyn_t* dyn_host, const float* state, const float* action, const float* sig, const float* Q,
+                         float* next_state, float* A, float* sig_prop, void* stream);
+
+/* measurement_fn's 12 x 12 Hessian at `state` for one batch [B,2], under the reference's differentiation rule:
+ * rays, ngp_nav_run_forward, loss, ngp_nav_run_backward, then one one-workgroup launch; 5 launches, no synchronisation.
+ * hessian [12,12]; grad [12], loss [1], dLdP [9] (each may be NULL): the gradient, the loss and the 3 x 3 matrix the contraction used; gradient and loss
+ * are bit for bit what an update = 0 iteration of ngp_filter_iterations writes.
+ * workspace: ngp_filter_workspace(B, num_steps) bytes, the layout of ngp_filter_iterations.  Reads start_state and sig_inv of cfg_host. */
+int ngp_filter_hessian(const ngp_nav_field_t* field_host, const void* prepared, const ngp_filter_cfg_t* cfg_host, const float* state,
+                       const float* target, const int32_t* batch, float* hessian, float* grad, float* loss, float* dLdP,
+                       void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

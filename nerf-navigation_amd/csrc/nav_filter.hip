@@ -391,3 +391,219 @@ extern "C" int ngp_filter_iterations(const ngp_nav_field_t* field, const void* p
     }
     return NGP_OK;
 }
+
+// ---------------------------------------------------------------------------
+// the rest of the estimator's time step (Estimator.estimate_state, nav/estimator_helpers.py:347-406; DESIGN.md §3.5 "Native time step"):
+//
+//   k_filter_propagate   Agent.drone_dynamics, its 12 x 12 Jacobian A (lane j carries the forward-mode tangent along state[j]) and (A sig) A^T + Q
+//   k_filter_hessian     measurement_fn's 12 x 12 Hessian under the reference's differentiation rule: the sums of k_filter_step in its order (the
+//                        gradient, the loss and dL/dP come out bit for bit as an update = 0 iteration writes them), then sum_ab (dL/dP)_ab d2 P_ab / dr_i dr_j
+//                        into H[6:9, 6:9] (one lane per (i, j), second-order forward mode) and Sinv + Sinv^T everywhere
+//
+// Both evaluate the formulas as written in float64 from the float32 inputs and round every output once (ngp_filter_step.h); one workgroup each.
+// ---------------------------------------------------------------------------
+#include "ngp_filter_step.h"
+
+__global__ __launch_bounds__(NF_THREADS) void k_filter_propagate(nfs_dyn D, const float* __restrict__ state, const float* __restrict__ action,
+                                                                 const float* __restrict__ sig, const float* __restrict__ Q,
+                                                                 float* __restrict__ next_state, float* __restrict__ A_out, float* __restrict__ sig_prop) {
+    __shared__ double A[144], AS[144];
+    const uint32_t tid = threadIdx.x;
+    if (tid < 12) {
+        nfs_d1 x[12], next[12];
+        double act[4];
+#pragma unroll
+        for (int k = 0; k < 12; k++) x[k] = nfs_d1((double)state[k], k == (int)tid ? 1.0 : 0.0);
+#pragma unroll
+        for (int k = 0; k < 4; k++) act[k] = (double)action[k];
+        nfs_drone_dynamics(D, x, act, next);
+#pragma unroll
+        for (int i = 0; i < 12; i++) {
+            A[i * 12 + tid] = next[i].d;
+            if (A_out) A_out[i * 12 + tid] = (float)next[i].d;
+            if (tid == 0) next_state[i] = (float)next[i].v;
+        }
+    }
+    if (!sig_prop) return;
+    __syncthreads();
+    const uint32_t i = tid / 12, j = tid % 12;
+    if (tid < 144) {
+        double s = 0.0;
+#pragma unroll
+        for (int k = 0; k < 12; k++) s += A[i * 12 + k] * (double)sig[k * 12 + j];
+        AS[tid] = s;
+    }
+    __syncthreads();
+    if (tid < 144) {
+        double s = 0.0;
+#pragma unroll
+        for (int k = 0; k < 12; k++) s += AS[i * 12 + k] * A[j * 12 + k];
+        sig_prop[tid] = (float)(s + (double)Q[tid]);
+    }
+}
+
+__global__ __launch_bounds__(NF_THREADS) void k_filter_hessian(nf_view V, nf_step_args A, const float* __restrict__ state, const int32_t* __restrict__ batch,
+                                                               uint32_t B, const float* __restrict__ grad_rays_o, const float* __restrict__ grad_rays_d,
+                                                               const float* __restrict__ partials, uint32_t n_partials, float* __restrict__ hessian,
+                                                               float* __restrict__ grad_out, float* __restrict__ loss_out, float* __restrict__ dLdP_out) {
+    __shared__ float sums[NF_WAVES][NF_SUMS];
+    __shared__ float x[12], delta[12], g_image[12], quad[12], mse;
+    __shared__ double h_image[9];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    if (tid < 12) {
+        const float s = state[tid];
+        x[tid] = s;
+        delta[tid] = s - A.start[tid];
+    }
+    // k_filter_step's sums, in its order
+    float acc[NF_SUMS];
+#pragma unroll
+    for (int k = 0; k < (int)NF_SUMS; k++) acc[k] = 0.0f;
+    ngp_camera unit;
+#pragma unroll
+    for (int e = 0; e < 9; e++) unit.r[e] = e % 4 == 0 ? 1.0f : 0.0f;
+    unit.t[0] = unit.t[1] = unit.t[2] = 0.0f;
+    unit.fx = V.fx; unit.fy = V.fy; unit.cx = V.cx; unit.cy = V.cy; unit.W = V.W; unit.H = V.H;
+    for (uint32_t n = tid; n < B; n += NF_THREADS) {
+        uint32_t row, col;
+        nf_pixel(batch, n, V.H, V.W, row, col);
+        float dir[3];
+        ngp_camera_ray(unit, row * V.W + col, dir);
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            acc[k] += grad_rays_o[3 * (size_t)n + k];
+            const float g = grad_rays_d[3 * (size_t)n + k];
+#pragma unroll
+            for (int j = 0; j < 3; j++) acc[3 + 3 * k + j] += g * dir[j];
+        }
+    }
+    for (uint32_t i = tid; i < n_partials; i += NF_THREADS) acc[12] += partials[i];
+#pragma unroll
+    for (int k = 0; k < (int)NF_SUMS; k++) acc[k] = nf_wave_sum(acc[k]);
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < (int)NF_SUMS; k++) sums[wave][k] = acc[k];
+    }
+    __syncthreads();
+    if (tid == 0) {
+        float tot[NF_SUMS];
+#pragma unroll
+        for (int k = 0; k < (int)NF_SUMS; k++) {
+            float s = sums[0][k];
+#pragma unroll
+            for (uint32_t w = 1; w < NF_WAVES; w++) s += sums[w][k];
+            tot[k] = s;
+        }
+        float xs[12];
+#pragma unroll
+        for (int k = 0; k < 12; k++) { xs[k] = x[k]; g_image[k] = 0.0f; }
+        nf_rodrigues Q;
+        float P[9], T[3], gr[3];
+        nf_pose(xs, Q, P, T);
+        nf_pose_backward(xs + 6, Q, tot + 3, gr);
+#pragma unroll
+        for (int i = 0; i < 3; i++) {
+            g_image[(i + 1) % 3] = tot[i];
+            g_image[6 + i] = gr[i];
+        }
+        mse = tot[12] / (float)(3ull * B);
+        if (dLdP_out) {
+#pragma unroll
+            for (int e = 0; e < 9; e++) dLdP_out[e] = tot[3 + e];
+        }
+    }
+    // the second wave meanwhile: lane 3 i + j takes d2 / dr_i dr_j of the camera rotation and contracts it with dL/dP (the same sums, added in the same order)
+    if (tid >= 64 && tid < 73) {
+        const int ij = (int)tid - 64, i = ij / 3, j = ij % 3;
+        nfs_d2 r[3], P[9];
+#pragma unroll
+        for (int k = 0; k < 3; k++) r[k] = nfs_d2((double)x[6 + k], k == i ? 1.0 : 0.0, k == j ? 1.0 : 0.0, 0.0);
+        nfs_measurement_rotation(r, (double)1e-10f, (double)NF_C90, P);
+        double h = 0.0;
+#pragma unroll
+        for (int e = 0; e < 9; e++) {
+            float s = sums[0][3 + e];
+#pragma unroll
+            for (uint32_t w = 1; w < NF_WAVES; w++) s += sums[w][3 + e];
+            h += (double)s * P[e].ab;
+        }
+        h_image[ij] = h;
+    }
+    double mg = 0.0;
+    if (tid < 12) {
+        double row = 0.0;
+#pragma unroll
+        for (int j = 0; j < 12; j++) {
+            const double dj = (double)delta[j];
+            row += (double)A.sig_inv[tid * 12 + j] * dj;
+            mg += ((double)A.sig_inv[tid * 12 + j] + (double)A.sig_inv[j * 12 + tid]) * dj;
+        }
+        quad[tid] = (float)((double)delta[tid] * row);
+    }
+    __syncthreads();
+    if (tid < 12 && grad_out) grad_out[tid] = g_image[tid] + (float)mg;
+    if (tid == 0 && loss_out) {
+        float process = quad[0];
+#pragma unroll
+        for (int k = 1; k < 12; k++) process += quad[k];
+        *loss_out = mse + process;
+    }
+    if (tid < 144) {
+        const uint32_t i = tid / 12, j = tid % 12;
+        double h = (double)A.sig_inv[i * 12 + j] + (double)A.sig_inv[j * 12 + i];
+        if (i >= 6 && i < 9 && j >= 6 && j < 9) h += h_image[(i - 6) * 3 + (j - 6)];
+        hessian[tid] = (float)h;
+    }
+}
+
+extern "C" int ngp_filter_propagate(const ngp_filter_dyn_t* dyn, const float* state, const float* action, const float* sig, const float* Q,
+                                    float* next_state, float* A, float* sig_prop, void* stream) {
+    NGP_REQUIRE(dyn, "filter_propagate: null cfg");
+    NGP_REQUIRE(state && action && next_state, "filter_propagate: null state / action / next_state");
+    NGP_REQUIRE(!sig_prop || (sig && Q), "filter_propagate: sig_prop needs sig and Q");
+    nfs_dyn D;
+    const int bad = nfs_dyn_prepare(dyn->dt, dyn->mass, dyn->g, dyn->I, D);
+    NGP_REQUIRE(bad != 1, "filter_propagate: dt = %g, mass = %g; both must be finite and > 0", (double)dyn->dt, (double)dyn->mass);
+    NGP_REQUIRE(bad != 2, "filter_propagate: the inertia matrix I is singular or not finite");
+    hipLaunchKernelGGL(k_filter_propagate, dim3(1), dim3(NF_THREADS), 0, (hipStream_t)stream, D, state, action, sig, Q, next_state, A, sig_prop);
+    NGP_CHECK_LAUNCH("filter_propagate");
+    return NGP_OK;
+}
+
+extern "C" int ngp_filter_hessian(const ngp_nav_field_t* field, const void* prepared, const ngp_filter_cfg_t* c, const float* state, const float* target,
+                                  const int32_t* batch, float* hessian, float* grad, float* loss, float* dLdP, void* workspace, size_t workspace_bytes,
+                                  void* stream) {
+    nf_view V;
+    const int rc_v = nf_view_of("filter_hessian", c, V);
+    if (rc_v != NGP_OK) return rc_v;
+    const uint32_t B = c->B, T = c->num_steps;
+    NGP_REQUIRE(T >= 1 && T <= NF_MAX_T, "filter_hessian: num_steps = %u; supported 1 <= num_steps <= 4096", T);
+    NGP_REQUIRE(state && target && batch && hessian, "filter_hessian: null state / target / batch / hessian");
+    const nf_ws w = nf_layout(B, T, workspace);
+    if (!workspace || workspace_bytes < w.total)
+        return ngp_fail(NGP_EWORKSPACE, "filter_hessian: workspace of %zu bytes, needs ngp_filter_workspace(B, num_steps) = %zu", workspace_bytes, w.total);
+    {   // the field is checked here, before anything is queued (N = 0 validates and launches nothing)
+        const int rc_f = ngp_nav_run_forward(field, prepared, w.rays_o, w.rays_d, w.nears, w.fars, 0, T, c->aabb, c->bg, w.image, w.depth, w.weights_sum,
+                                             w.saved, w.saved_bytes, stream);
+        if (rc_f != NGP_OK) return rc_f;
+    }
+    nf_step_args A = {};
+    for (int k = 0; k < 12; k++) A.start[k] = c->start_state[k];
+    for (int k = 0; k < 144; k++) A.sig_inv[k] = c->sig_inv[k];
+    const uint32_t blocks = ngp_div_up(B, NF_THREADS);
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_filter_rays, dim3(blocks), dim3(NF_THREADS), 0, s, V, state, batch, B, w.rays_o, w.rays_d, w.nears, w.fars);
+    NGP_CHECK_LAUNCH("filter_hessian: rays");
+    int rc = ngp_nav_run_forward(field, prepared, w.rays_o, w.rays_d, w.nears, w.fars, B, T, c->aabb, c->bg, w.image, w.depth, w.weights_sum, w.saved,
+                                 w.saved_bytes, stream);
+    if (rc != NGP_OK) return rc;
+    hipLaunchKernelGGL(k_filter_loss, dim3(blocks), dim3(NF_THREADS), 0, s, (const float*)w.image, target, batch, B, c->H, c->W, w.grad_image, w.partials);
+    NGP_CHECK_LAUNCH("filter_hessian: loss");
+    rc = ngp_nav_run_backward(field, prepared, w.rays_o, w.rays_d, w.nears, w.fars, B, T, c->aabb, c->bg, w.grad_image, nullptr, nullptr, w.saved,
+                              w.saved_bytes, w.grad_rays_o, w.grad_rays_d, stream);
+    if (rc != NGP_OK) return rc;
+    hipLaunchKernelGGL(k_filter_hessian, dim3(1), dim3(NF_THREADS), 0, s, V, A, state, batch, B, (const float*)w.grad_rays_o, (const float*)w.grad_rays_d,
+                       (const float*)w.partials, blocks, hessian, grad, loss, dLdP);
+    NGP_CHECK_LAUNCH("filter_hessian: hessian");
+    return NGP_OK;
+}

@@ -637,6 +637,52 @@ def _measurement_pose(state):
     return pose
 
 
+def drone_dynamics(state, action, dt, mass, g, I):
+    """Agent.drone_dynamics (nav/agent_helpers.py:124-171) restated in torch: state [12] (position, velocity, rotation vector, body rate), action [4]
+    (thrust, torque) -> the next state [12].  Differentiable, in the dtype and on the device of `state`, with the reference's branches: vec_to_rot_matrix's
+    `1e-10 + angle` guard, the identity (a constant) when the angle displacement is exactly 0, rot_matrix_to_vec with acos_safe's straight line beyond
+    |x| = 1 - 1e-7 and the zero vector (a constant) where the angle is exactly 0.  csrc/nav_filter.hip's k_filter_propagate evaluates the same formulas in
+    float64; this is the torch route of the tools and the restatement the tests hold against the executed reference."""
+    import numpy as np
+    kw = dict(dtype=state.dtype, device=state.device)
+    I = torch.as_tensor(I).to(**kw)
+    invI = torch.inverse(I)
+    fz, tau = action[0], action[1:]
+    pos, v, omega = state[0:3], state[3:6], state[9:]
+    # vec_to_rot_matrix (nav/math_utils.py:159-174)
+    angle = torch.norm(state[6:9], dim=-1, keepdim=True)
+    S = _hat(state[6:9] / (1e-10 + angle))
+    angle = angle[..., None]
+    R = torch.eye(3, **kw) + torch.sin(angle) * S + (1 - torch.cos(angle)) * S @ S
+    sum_action = torch.cat([torch.zeros(2, **kw), fz.reshape(1)])
+    dv = (torch.tensor([0., 0., -mass * g], **kw) + R @ sum_action) / mass
+    domega = invI @ (tau - torch.linalg.cross(omega, I @ omega))
+    # the exponential map of the angle displacement
+    step = omega * dt
+    theta = torch.norm(step, p=2)
+    if theta == 0:
+        exp_i = torch.eye(3, **kw)
+    else:
+        K = _hat(step / theta)
+        exp_i = torch.eye(3, **kw) + torch.sin(theta) * K + (1 - torch.cos(theta)) * torch.matmul(K, K)
+    next_R = R @ exp_i
+    # rot_matrix_to_vec (nav/math_utils.py:116-157)
+    eps = 1e-7
+    x = (torch.diagonal(next_R).sum(-1) - 1) / 2
+    if abs(x) <= 1 - eps:
+        angle = torch.acos(x)
+    else:
+        slope = np.arccos(1 - eps) / eps
+        sign = torch.sign(x).detach()
+        angle = torch.acos(sign * (1 - eps)) - slope * sign * (abs(x) - 1 + eps)
+    angle = angle.reshape(1)
+    if angle[0] == 0:
+        vec = torch.zeros(3, **kw)
+    else:
+        vec = 1 / (2 * torch.sin(angle + 1e-10)) * torch.stack([next_R[2, 1] - next_R[1, 2], next_R[0, 2] - next_R[2, 0], next_R[1, 0] - next_R[0, 1]], dim=-1)
+    return torch.cat([pos + v * dt, v + dv * dt, angle * vec, omega + domega * dt])
+
+
 def nearest_pd(A):
     """The nearest positive-definite matrix in the Frobenius norm (N. J. Higham, "Computing a nearest symmetric positive semidefinite matrix", 1988),
     as Estimator.estimate_state uses it (nav/math_utils.py:40-86): the symmetric part B of A, averaged with its polar factor H (from the SVD of B),
@@ -672,15 +718,22 @@ class NativePoseFilter:
     """Estimator (nav/estimator_helpers.py) with its optimisation loop native: measurement_fn -> backward -> Adam run as ngp_filter_iterations, i.e. per
     iteration one launch for the batch's rays from the state, NativeNavQueries' run kernel forward, one launch for the loss, the run kernel backward
     and one launch for the chain back to the state, the Mahalanobis term and the Adam step.  `filter_cfg` takes the reference's keys batch_size,
-    lrate, N_iter, sig0, Q.  The feature detector, its dilation and the agent's dynamics stay with the caller, who hands over `interest_regions`
+    lrate, N_iter, sig0, Q.  The feature detector and its dilation stay with the caller, who hands over `interest_regions`
     ([M,2] (row, col) pairs) or ready batches; loss, state and gradient histories are device tensors.
 
         filt = NativePoseFilter(filter_cfg, queries, start_state)          # queries: NativeNavQueries
         batches = filt.draw_batches(interest_regions, filt.iter, rng)
         xt = filt.estimate_relative_pose(target, xt_propagated, sig_propagated, batches)
+
+    With `agent_cfg` (the reference's keys dt, mass, g, I) the whole time step of Estimator.estimate_state is native (csrc/nav_filter.hip, DESIGN 3.5
+    "Native time step"): the dynamics, their Jacobian and the covariance propagation in one launch, the loop, and the Hessian in five launches; one host
+    step per time step (nearest_pd) and nothing in torch autograd.
+
+        filt = NativePoseFilter(filter_cfg, queries, start_state, agent_cfg)
+        xt = filt.estimate_state(target, action, interest_regions, rng=rng)  # filt.xt, filt.sig are the posterior
     """
 
-    def __init__(self, filter_cfg, queries, start_state=None):
+    def __init__(self, filter_cfg, queries, start_state=None, agent_cfg=None):
         if not isinstance(queries, NativeNavQueries):
             raise ValueError(f"NativePoseFilter needs a NativeNavQueries (the fused float32 queries), got {type(queries).__name__}")
         self.queries = queries
@@ -693,6 +746,11 @@ class NativePoseFilter:
         self.target = self.batch = None
         self.sig_inv = None                                  # the float32 inverse covariance of the last call, [12,12] on the host
         self._ws = None
+        self.agent_cfg = agent_cfg
+        # estimate_state's records (nav/estimator_helpers.py:164-171).  The reference's `covariance` list is `covariance_estimate` here: `covariance` is the method.
+        self.action = self.covariance_estimate = self.state_estimate = None
+        self.iteration = 0
+        self.hessian_grad = self.hessian_loss = self.hessian_dLdP = None
 
     # -- plumbing ------------------------------------------------------------------------------------------------------
     def _vec(self, v):
@@ -851,13 +909,106 @@ class NativePoseFilter:
         rgb = self.queries.render_fn(rays_o.reshape(1, -1, 3), rays_d.reshape(1, -1, 3))["image"].reshape(-1, 3)
         return torch.nn.functional.mse_loss(rgb, target[rows, cols]) + process
 
-    def measurement_hessian(self, state, start_state, sig):
+    def measurement_hessian(self, state, start_state, sig, native=False):
         """the 12 x 12 Hessian estimate_state asks for once per time step (nav/estimator_helpers.py:384), at the target and the last batch of
-        estimate_relative_pose; through torch.autograd.functional.hessian, as in the reference"""
+        estimate_relative_pose.  Default: through torch.autograd.functional.hessian over the queries, as in the reference.  native=True: ngp_filter_hessian
+        (five launches, float64 second derivatives of the pose chain, rounded once) -> [12,12] float32 on the device; the gradient, the loss and the
+        3 x 3 matrix dL/dP of that call are kept as hessian_grad, hessian_loss and hessian_dLdP."""
         if self.target is None or self.batch is None:
             raise RuntimeError("measurement_hessian needs the target and batch of an estimate_relative_pose call")
+        if native:
+            res = self.hessian_and_gradient(state, start_state, sig, self.target, self.batch)
+            self.hessian_grad, self.hessian_loss, self.hessian_dLdP = res["grad"], res["loss"], res["dLdP"]
+            return res["hessian"]
         start, sig = self._vec(start_state), torch.as_tensor(sig).detach().to(self.device, torch.float32)
         return torch.autograd.functional.hessian(lambda x: self.measurement_fn(x, start, sig, self.target, self.batch), self._vec(state).clone())
+
+    def hessian_and_gradient(self, state, start_state, sig, target, batch):
+        """ngp_filter_hessian: measurement_fn's Hessian [12,12], gradient [12], loss and the 3 x 3 matrix dL/dP the image term was contracted with, at
+        `state` for one batch [B,2]; device tensors, no synchronisation.  grad and loss are bit for bit cost_and_gradient's."""
+        import ctypes
+        import ngp_hip as _hip
+        batch = self._batches(batch)[0]
+        B = int(batch.shape[0])
+        target = self._target(target)
+        kw = dict(dtype=torch.float32, device=self.device)
+        out = dict(hessian=torch.empty(12, 12, **kw), grad=torch.empty(12, **kw), loss=torch.empty(1, **kw), dLdP=torch.empty(3, 3, **kw))
+        st, prep = self.queries.native.struct()
+        c = self._cfg_struct(B, start_state, sig)
+        ws = self._workspace(B)
+        _hip.check(_hip.lib().ngp_filter_hessian(ctypes.byref(st), _hip.ptr(prep), ctypes.byref(c), _hip.ptr(self._vec(state).contiguous()),
+                                                 _hip.ptr(target), _hip.ptr(batch), _hip.ptr(out["hessian"]), _hip.ptr(out["grad"]), _hip.ptr(out["loss"]),
+                                                 _hip.ptr(out["dLdP"]), _hip.ptr(ws), ws.numel(), _hip.stream()), "filter_hessian")
+        out["loss"] = out["loss"][0]
+        return out
+
+    def _dyn_struct(self):
+        import ngp_hip as _hip
+        if self.agent_cfg is None:
+            raise ValueError("propagate needs agent_cfg (dt, mass, g, I): NativePoseFilter(filter_cfg, queries, start_state, agent_cfg)")
+        a = self.agent_cfg
+        d = _hip.ngp_filter_dyn_t()
+        d.dt, d.mass, d.g = float(a["dt"]), float(a["mass"]), float(a["g"])
+        d.I[:] = [float(v) for v in torch.as_tensor(a["I"]).detach().cpu().reshape(-1).tolist()]
+        return d
+
+    def propagate(self, state, action, sig=None, Q=None):
+        """Agent.drone_dynamics at `state` [12] under `action` [4], its Jacobian A and, with sig and Q, sig_prop = (A sig) A^T + Q
+        (nav/estimator_helpers.py:355-369) in ONE launch (ngp_filter_propagate): dict(state [12], A [12,12], sig_prop [12,12] or None), float32 on the
+        device.  A is taken at `state`, the point the dynamics are evaluated at."""
+        import ctypes
+        import ngp_hip as _hip
+        d = self._dyn_struct()
+        kw = dict(dtype=torch.float32, device=self.device)
+        x = self._vec(state).contiguous()
+        act = torch.as_tensor(action).detach().to(self.device, torch.float32).reshape(4).contiguous()
+        if (sig is None) != (Q is None):
+            raise ValueError("propagate takes sig and Q together")
+        mats = [None if m is None else torch.as_tensor(m).detach().to(self.device, torch.float32).reshape(12, 12).contiguous() for m in (sig, Q)]
+        out = dict(state=torch.empty(12, **kw), A=torch.empty(12, 12, **kw), sig_prop=torch.empty(12, 12, **kw) if sig is not None else None)
+        _hip.check(_hip.lib().ngp_filter_propagate(ctypes.byref(d), _hip.ptr(x), _hip.ptr(act), _hip.ptr(mats[0]), _hip.ptr(mats[1]), _hip.ptr(out["state"]),
+                                                   _hip.ptr(out["A"]), _hip.ptr(out["sig_prop"]), _hip.stream()), "filter_propagate")
+        return out
+
+    def estimate_state(self, target, action, interest_regions=None, batches=None, rng=None):
+        """Estimator.estimate_state (nav/estimator_helpers.py:347-406): propagate the estimate and its covariance through the dynamics, run the loop from
+        there, take the Hessian at the result and make its nearest positive-definite matrix's inverse the new covariance.  target: the sensor image,
+        float32 [H,W,3] on the GPU; the loop's batches are drawn from `interest_regions` ([M,2] (row, col) pairs, with `rng`, a numpy Generator) unless
+        `batches` [N_iter,B,2] are given.  Empty interest_regions and no batches: the reference's "feature detection failed" path (:185-190, :381) -- the
+        propagated state is returned, no loop and no Hessian run, and `sig` stays the previous posterior.  Keeps xt, sig, action, covariance_estimate,
+        state_estimate, iteration.  One difference from the reference: A is the Jacobian at the previous estimate (the point the dynamics are evaluated
+        at, one launch), where :362 evaluates it at the propagated one."""
+        import numpy as np
+        if self.xt is None:
+            raise ValueError("estimate_state needs the estimate of the previous time step: NativePoseFilter(filter_cfg, queries, start_state, agent_cfg)")
+        prop = self.propagate(self.xt, action, self.sig, self.Q)
+        xt_prop, sig_prop = prop["state"], prop["sig_prop"]
+        self.action = torch.as_tensor(action).detach().cpu().reshape(-1).tolist()
+        if batches is None:
+            regions = np.zeros((0, 2), np.int64) if interest_regions is None else np.asarray(interest_regions)
+            if regions.size:
+                batches = self.draw_batches(regions, self.iter, np.random.default_rng() if rng is None else rng)
+        if batches is None:
+            self.losses, self.states = [], []
+            xt = xt_prop.clone()
+        else:
+            xt = self.estimate_relative_pose(target, xt_prop, sig_prop, batches)
+            hess = self.measurement_hessian(xt, xt_prop, sig_prop, native=True)
+            self.sig = self.covariance(hess).float().to(self.device)
+        self.xt = xt
+        self.covariance_estimate = torch.as_tensor(self.sig).detach().cpu().tolist()
+        self.state_estimate = xt.detach().cpu().tolist()
+        self.iteration += 1
+        return xt.clone()
+
+    def save_data(self, filename):
+        """Estimator.save_data (nav/estimator_helpers.py:408-419): the last time step as JSON under the reference's keys"""
+        import json
+        as_list = lambda v: v.detach().cpu().tolist() if isinstance(v, torch.Tensor) else v      # noqa: E731
+        data = {"loss": as_list(self.losses), "covariance": self.covariance_estimate, "state_estimate": self.state_estimate,
+                "grad_states": as_list(self.states), "action": self.action}
+        with open(filename, "w+") as f:
+            json.dump(data, f, indent=4)
 
     def covariance(self, hessian):
         """estimate_state's covariance update (nav/estimator_helpers.py:387-394): the inverse of the positive-definite matrix nearest to the Hessian,

@@ -141,6 +141,8 @@ _SIGNATURES = {
     "ngp_filter_workspace": (c_sz, [c_u32, c_u32]),
     "ngp_filter_iterations": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_u32, c_u32, c_int, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "ngp_filter_rays": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "ngp_filter_propagate": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "ngp_filter_hessian": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
 }
 
 EXPORTS = tuple(_SIGNATURES)
@@ -191,6 +193,11 @@ class ngp_filter_cfg_t(ctypes.Structure):
     _fields_ = [("H", c_u32), ("W", c_u32), ("intrinsics", c_f32 * 4), ("aabb", c_f32 * 6), ("min_near", c_f32), ("num_steps", c_u32),
                 ("bg", c_f32 * 3), ("B", c_u32), ("start_state", c_f32 * 12), ("sig_inv", c_f32 * 144), ("lr", ctypes.c_double),
                 ("beta1", ctypes.c_double), ("beta2", ctypes.c_double), ("eps", ctypes.c_double)]
+
+
+class ngp_filter_dyn_t(ctypes.Structure):
+    """include/ngp_hip.h: ngp_filter_dyn_t"""
+    _fields_ = [("dt", c_f32), ("mass", c_f32), ("g", c_f32), ("I", c_f32 * 9)]
 
 
 FILTER_ADAM_FLOATS = 37                                      # include/ngp_hip.h: NGP_FILTER_ADAM_FLOATS
