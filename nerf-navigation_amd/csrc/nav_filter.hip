@@ -8,11 +8,16 @@
 //   k_filter_step     one workgroup: sum grad_rays_o, sum grad_rays_d (x) dir (= dL/dP, since rays_d = P dir) and the loss partials; one thread chains them
 //                     back through the axis matrices and the Rodrigues formula; the Mahalanobis term; the records; torch.optim.Adam's step.
 //
+// Shared: the sums, the chain back to the state, the Mahalanobis row and the loss are nf_ray_sums .. nf_loss below, one copy for k_filter_step and
+// k_filter_hessian; nf_begin and nf_measure are the host side the two loop entry points have in common; the Adam step and the wave sum are the
+// planner's too (ngp_nav_step.h: ngp_adam_step, ngp_wave_sum); the axis matrices and the 3 x 3 product are ngp_filter_step.h's, at T = float.
+//
 // The derivative conventions are torch autograd's of the formula as written (nav/math_utils.py:159-174): R = I + sin(a) K + ((1 - cos(a)) K) K,
 // K = hat(r / (1e-10 + a)), a = |r|, with the denominator's dependence on a kept and a zero subgradient of the norm at r = 0.  No gradient flows through
 // near / far (nerf/renderer.py:140-141).  No atomics; every sum runs in a fixed order, so two runs are bit-identical.
-#include "ngp_device.h"
+#include "ngp_nav_step.h"
 #include "ngp_camera.h"
+#include "ngp_filter_step.h"
 
 static constexpr uint32_t NF_THREADS = 256, NF_WAVES = NF_THREADS / 64;
 static constexpr uint32_t NF_MAX_B = 1u << 20, NF_MAX_T = 4096;             // num_steps: what ngp_nav_run_forward accepts
@@ -26,18 +31,11 @@ static_assert(NGP_FILTER_ADAM_FLOATS == NF_STEP + 1, "adam_state layout");
 struct nf_view { float fx, fy, cx, cy; uint32_t W, H; float aabb[6]; float min_near; };
 struct nf_step_args {
     float start[12], sig_inv[144];
-    float lr, beta1, beta2, w1, w2, eps;                                     // Adam: w1 = (float)(1 - beta1), w2 = (float)(1 - beta2) formed in float64
+    ngp_adam_coef adam;                                                      // zeroed where no step is taken (ngp_filter_hessian)
 };
 
 // vec_to_rot_matrix (nav/math_utils.py:159-174) and what its backward needs
 struct nf_rodrigues { float K[9], M[9], R[9], a, d, sn, cs; };
-
-__device__ __forceinline__ void nf_matmul3(const float* A, const float* B, float* C) {
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-#pragma unroll
-        for (int j = 0; j < 3; j++) C[i * 3 + j] = (A[i * 3 + 0] * B[0 * 3 + j] + A[i * 3 + 1] * B[1 * 3 + j]) + A[i * 3 + 2] * B[2 * 3 + j];
-}
 
 __device__ __forceinline__ void nf_rotation(const float* r, nf_rodrigues& Q) {
     Q.a = sqrtf((r[0] * r[0] + r[1] * r[1]) + r[2] * r[2]);
@@ -49,7 +47,7 @@ __device__ __forceinline__ void nf_rotation(const float* r, nf_rodrigues& Q) {
 #pragma unroll
     for (int e = 0; e < 9; e++) { Q.K[e] = K[e]; Q.M[e] = omc * K[e]; }
     float MK[9];
-    nf_matmul3(Q.M, Q.K, MK);
+    nfs_matmul3(Q.M, Q.K, MK);
 #pragma unroll
     for (int e = 0; e < 9; e++) Q.R[e] = ((e % 4 == 0 ? 1.0f : 0.0f) + Q.sn * K[e]) + MK[e];
 }
@@ -58,19 +56,9 @@ __device__ __forceinline__ void nf_rotation(const float* r, nf_rodrigues& Q) {
 __device__ __forceinline__ void nf_pose(const float* state, nf_rodrigues& Q, float* P, float* T) {
     const float r[3] = {state[6], state[7], state[8]};
     nf_rotation(r, Q);
-    float Rb[9];
+    nfs_camera_axes(Q.R, (double)NF_C90, P);
 #pragma unroll
-    for (int j = 0; j < 3; j++) {
-        Rb[0 + j] = Q.R[0 + j];
-        Rb[3 + j] = NF_C90 * Q.R[3 + j] - Q.R[6 + j];
-        Rb[6 + j] = Q.R[3 + j] + NF_C90 * Q.R[6 + j];
-    }
-#pragma unroll
-    for (int i = 0; i < 3; i++) {
-        const int m = (i + 1) % 3;
-        P[i * 3 + 0] = Rb[m * 3 + 0]; P[i * 3 + 1] = -Rb[m * 3 + 1]; P[i * 3 + 2] = -Rb[m * 3 + 2];
-        T[i] = state[m];
-    }
+    for (int i = 0; i < 3; i++) T[i] = state[(i + 1) % 3];
 }
 
 // the backward of nf_pose's rotation part: GP = dL/dP -> dL/d state[6:9]
@@ -93,8 +81,8 @@ __device__ __forceinline__ void nf_pose_backward(const float* r, const nf_rodrig
     for (int i = 0; i < 3; i++)
 #pragma unroll
         for (int j = 0; j < 3; j++) { Kt[i * 3 + j] = Q.K[j * 3 + i]; Mt[i * 3 + j] = Q.M[j * 3 + i]; }
-    nf_matmul3(GR, Kt, GM);
-    nf_matmul3(Mt, GR, GK);
+    nfs_matmul3(GR, Kt, GM);
+    nfs_matmul3(Mt, GR, GK);
     const float omc = 1.0f - Q.cs;
     float g_sn = 0.0f, g_omc = 0.0f;
 #pragma unroll
@@ -126,10 +114,106 @@ __device__ __forceinline__ void nf_pixel(const int32_t* __restrict__ batch, uint
     col = (uint32_t)(c < 0 ? 0 : c >= (int32_t)W ? (int32_t)W - 1 : c);
 }
 
-__device__ __forceinline__ float nf_wave_sum(float v) {
+// ---------------------------------------------------------------------------
+// what k_filter_step and k_filter_hessian have in common: one workgroup's LDS and the passes over it.  Every sum is written once, here, so the gradient,
+// the loss and dL/dP of the Hessian call are an update = 0 iteration's bit for bit
+// ---------------------------------------------------------------------------
+
+struct nf_shared { float sums[NF_WAVES][NF_SUMS], x[12], delta[12], g_image[12], quad[12], mse; };
+
+__device__ __forceinline__ void nf_load_state(nf_shared& S, const nf_step_args& A, const float* __restrict__ state) {
+    const uint32_t tid = threadIdx.x;
+    if (tid < 12) {
+        const float s = state[tid];
+        S.x[tid] = s;
+        S.delta[tid] = s - A.start[tid];
+    }
+}
+
+// per-lane sums over the rays (lanes strided over them) and the loss partials, then a fixed butterfly; lane 0 of each wave stores its 13 sums
+__device__ __forceinline__ void nf_ray_sums(nf_shared& S, const nf_view& V, const int32_t* __restrict__ batch, uint32_t B,
+                                            const float* __restrict__ grad_rays_o, const float* __restrict__ grad_rays_d,
+                                            const float* __restrict__ partials, uint32_t n_partials) {
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    float acc[NF_SUMS];
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
+    for (int k = 0; k < (int)NF_SUMS; k++) acc[k] = 0.0f;
+    ngp_camera unit;                                                         // identity pose: ngp_camera_ray returns the pixel's unit direction
+#pragma unroll
+    for (int e = 0; e < 9; e++) unit.r[e] = e % 4 == 0 ? 1.0f : 0.0f;
+    unit.t[0] = unit.t[1] = unit.t[2] = 0.0f;
+    unit.fx = V.fx; unit.fy = V.fy; unit.cx = V.cx; unit.cy = V.cy; unit.W = V.W; unit.H = V.H;
+    for (uint32_t n = tid; n < B; n += NF_THREADS) {
+        uint32_t row, col;
+        nf_pixel(batch, n, V.H, V.W, row, col);
+        float dir[3];
+        ngp_camera_ray(unit, row * V.W + col, dir);
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            acc[k] += grad_rays_o[3 * (size_t)n + k];
+            const float g = grad_rays_d[3 * (size_t)n + k];
+#pragma unroll
+            for (int j = 0; j < 3; j++) acc[3 + 3 * k + j] += g * dir[j];
+        }
+    }
+    for (uint32_t i = tid; i < n_partials; i += NF_THREADS) acc[12] += partials[i];
+#pragma unroll
+    for (int k = 0; k < (int)NF_SUMS; k++) acc[k] = ngp_wave_sum(acc[k]);
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < (int)NF_SUMS; k++) S.sums[wave][k] = acc[k];
+    }
+}
+
+// sum k of the whole workgroup: the waves in order
+__device__ __forceinline__ float nf_total(const nf_shared& S, int k) {
+    float s = S.sums[0][k];
+#pragma unroll
+    for (uint32_t w = 1; w < NF_WAVES; w++) s += S.sums[w][k];
+    return s;
+}
+
+// one lane, after the barrier: the totals (left in tot: grad_rays_o [3], dL/dP [9], squared error), dL/dP chained back to the state, mse
+__device__ __forceinline__ void nf_image_gradient(nf_shared& S, uint32_t B, float* tot) {
+#pragma unroll
+    for (int k = 0; k < (int)NF_SUMS; k++) tot[k] = nf_total(S, k);
+    float xs[12];
+#pragma unroll
+    for (int k = 0; k < 12; k++) { xs[k] = S.x[k]; S.g_image[k] = 0.0f; }
+    nf_rodrigues Q;
+    float P[9], T[3], gr[3];
+    nf_pose(xs, Q, P, T);
+    nf_pose_backward(xs + 6, Q, tot + 3, gr);
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+        S.g_image[(i + 1) % 3] = tot[i];                                    // T[i] = position[(i + 1) % 3]
+        S.g_image[6 + i] = gr[i];
+    }
+    S.mse = tot[12] / (float)(3ull * B);
+}
+
+// lanes 0-11, Mahalanobis: row tid of delta^T Sinv delta into quad, and (returned) of its gradient (Sinv + Sinv^T) delta; float64 sums
+__device__ __forceinline__ double nf_process_row(nf_shared& S, const nf_step_args& A) {
+    const uint32_t tid = threadIdx.x;
+    double mg = 0.0;
+    if (tid < 12) {
+        double row = 0.0;
+#pragma unroll
+        for (int j = 0; j < 12; j++) {
+            const double dj = (double)S.delta[j];
+            row += (double)A.sig_inv[tid * 12 + j] * dj;
+            mg += ((double)A.sig_inv[tid * 12 + j] + (double)A.sig_inv[j * 12 + tid]) * dj;
+        }
+        S.quad[tid] = (float)((double)S.delta[tid] * row);
+    }
+    return mg;
+}
+
+__device__ __forceinline__ float nf_loss(const nf_shared& S) {
+    float process = S.quad[0];
+#pragma unroll
+    for (int k = 1; k < 12; k++) process += S.quad[k];
+    return S.mse + process;
 }
 
 // ---------------------------------------------------------------------------
@@ -178,7 +262,7 @@ __global__ __launch_bounds__(NF_THREADS) void k_filter_loss(const float* __restr
         }
         sq = (e[0] * e[0] + e[1] * e[1]) + e[2] * e[2];
     }
-    sq = nf_wave_sum(sq);
+    sq = ngp_wave_sum(sq);
     if ((threadIdx.x & 63u) == 0) wave_sums[threadIdx.x >> 6] = sq;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -189,118 +273,38 @@ __global__ __launch_bounds__(NF_THREADS) void k_filter_loss(const float* __restr
     }
 }
 
-// one element of torch.optim.Adam(capturable=True)'s step: k_plan_cost_step's arithmetic (nav_plan.hip np_adam), restated here so that
-// that kernel's code is not touched; bc1, bc2 = beta^step are the same for the 12 entries
-__device__ __forceinline__ float nf_adam(const nf_step_args& A, float param, float grad, float* m, float* v, float step) {
-    *m = *m + A.w1 * (grad - *m);
-    *v = *v * A.beta2 + A.w2 * (grad * grad);
-    float bc1 = powf(A.beta1, step), bc2 = powf(A.beta2, step);
-    bc1 = bc1 - 1.0f; bc2 = -(bc2 - 1.0f);
-    const float step_size = 1.0f / (bc1 / A.lr);
-    const float bc2_sqrt = sqrtf(bc2);
-    const float denom = (sqrtf(*v) / bc2_sqrt + A.eps) / step_size;
-    return param + *m / denom;
-}
-
 __global__ __launch_bounds__(NF_THREADS) void k_filter_step(nf_view V, nf_step_args A, int update, float* __restrict__ state, float* __restrict__ adam,
                                                             const int32_t* __restrict__ batch, uint32_t B, const float* __restrict__ grad_rays_o,
                                                             const float* __restrict__ grad_rays_d, const float* __restrict__ partials,
                                                             uint32_t n_partials, float* __restrict__ loss_out, float* __restrict__ state_out,
                                                             float* __restrict__ grad_out) {
-    __shared__ float sums[NF_WAVES][NF_SUMS];
-    __shared__ float x[12], delta[12], g_image[12], quad[12], mse;
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    __shared__ nf_shared S;
+    const uint32_t tid = threadIdx.x;
     const float step = adam[NF_STEP] + 1.0f;                                 // read before any lane writes it (there are barriers in between)
-    if (tid < 12) {
-        const float s = state[tid];
-        x[tid] = s;
-        delta[tid] = s - A.start[tid];
-    }
-    // per-lane sums over the rays (lanes strided over them), then a fixed butterfly and the waves in order
-    float acc[NF_SUMS];
-#pragma unroll
-    for (int k = 0; k < (int)NF_SUMS; k++) acc[k] = 0.0f;
-    ngp_camera unit;                                                         // identity pose: ngp_camera_ray returns the pixel's unit direction
-#pragma unroll
-    for (int e = 0; e < 9; e++) unit.r[e] = e % 4 == 0 ? 1.0f : 0.0f;
-    unit.t[0] = unit.t[1] = unit.t[2] = 0.0f;
-    unit.fx = V.fx; unit.fy = V.fy; unit.cx = V.cx; unit.cy = V.cy; unit.W = V.W; unit.H = V.H;
-    for (uint32_t n = tid; n < B; n += NF_THREADS) {
-        uint32_t row, col;
-        nf_pixel(batch, n, V.H, V.W, row, col);
-        float dir[3];
-        ngp_camera_ray(unit, row * V.W + col, dir);
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-            acc[k] += grad_rays_o[3 * (size_t)n + k];
-            const float g = grad_rays_d[3 * (size_t)n + k];
-#pragma unroll
-            for (int j = 0; j < 3; j++) acc[3 + 3 * k + j] += g * dir[j];
-        }
-    }
-    for (uint32_t i = tid; i < n_partials; i += NF_THREADS) acc[12] += partials[i];
-#pragma unroll
-    for (int k = 0; k < (int)NF_SUMS; k++) acc[k] = nf_wave_sum(acc[k]);
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < (int)NF_SUMS; k++) sums[wave][k] = acc[k];
-    }
+    nf_load_state(S, A, state);
+    nf_ray_sums(S, V, batch, B, grad_rays_o, grad_rays_d, partials, n_partials);
     __syncthreads();
     if (tid == 0) {
         float tot[NF_SUMS];
-#pragma unroll
-        for (int k = 0; k < (int)NF_SUMS; k++) {
-            float s = sums[0][k];
-#pragma unroll
-            for (uint32_t w = 1; w < NF_WAVES; w++) s += sums[w][k];
-            tot[k] = s;
-        }
-        float xs[12];
-#pragma unroll
-        for (int k = 0; k < 12; k++) { xs[k] = x[k]; g_image[k] = 0.0f; }
-        nf_rodrigues Q;
-        float P[9], T[3], gr[3];
-        nf_pose(xs, Q, P, T);
-        nf_pose_backward(xs + 6, Q, tot + 3, gr);
-#pragma unroll
-        for (int i = 0; i < 3; i++) {
-            g_image[(i + 1) % 3] = tot[i];                                  // T[i] = position[(i + 1) % 3]
-            g_image[6 + i] = gr[i];
-        }
-        mse = tot[12] / (float)(3ull * B);
+        nf_image_gradient(S, B, tot);
     }
-    double mg = 0.0;
-    if (tid < 12) {                                                          // Mahalanobis: delta^T Sinv delta and its gradient (Sinv + Sinv^T) delta
-        double row = 0.0;
-#pragma unroll
-        for (int j = 0; j < 12; j++) {
-            const double dj = (double)delta[j];
-            row += (double)A.sig_inv[tid * 12 + j] * dj;
-            mg += ((double)A.sig_inv[tid * 12 + j] + (double)A.sig_inv[j * 12 + tid]) * dj;
-        }
-        quad[tid] = (float)((double)delta[tid] * row);
-    }
+    const double mg = nf_process_row(S, A);
     __syncthreads();
     if (tid < 12) {
-        const float g = g_image[tid] + (float)mg;
-        const float s = x[tid];
+        const float g = S.g_image[tid] + (float)mg;
+        const float s = S.x[tid];
         adam[NF_G + tid] = g;
         if (grad_out) grad_out[tid] = g;
         if (state_out) state_out[tid] = s;
-        if (update) {
+        if (update) {                                                        // bc1, bc2 = beta^step are the same for the 12 entries
             float m = adam[NF_M + tid], v = adam[NF_V + tid];
-            state[tid] = nf_adam(A, s, g, &m, &v, step);
+            state[tid] = ngp_adam_step(A.adam, s, g, &m, &v, step);
             adam[NF_M + tid] = m;
             adam[NF_V + tid] = v;
         }
     }
     if (tid == 0) {
-        if (loss_out) {
-            float process = quad[0];
-#pragma unroll
-            for (int k = 1; k < 12; k++) process += quad[k];
-            *loss_out = mse + process;
-        }
+        if (loss_out) *loss_out = nf_loss(S);
         if (update) adam[NF_STEP] = step;
     }
 }
@@ -347,45 +351,68 @@ extern "C" int ngp_filter_rays(const ngp_filter_cfg_t* c, const float* state, co
     return NGP_OK;
 }
 
+// what the two entry points of the loop do before they queue anything, in this order: the view, the shape, the entry point's own null-pointer refusal
+// (`null_refusal`: its message, or NULL where every pointer is there), the workspace, the field (N = 0 validates and launches nothing), and the
+// start state and inverse covariance the last kernel takes as arguments (A.adam is left zeroed)
+static int nf_begin(const char* who, const char* null_refusal, const ngp_nav_field_t* field, const void* prepared, const ngp_filter_cfg_t* c,
+                    void* workspace, size_t workspace_bytes, void* stream, nf_view& V, nf_ws& w, nf_step_args& A) {
+    const int rc_v = nf_view_of(who, c, V);
+    if (rc_v != NGP_OK) return rc_v;
+    const uint32_t T = c->num_steps;
+    NGP_REQUIRE(T >= 1 && T <= NF_MAX_T, "%s: num_steps = %u; supported 1 <= num_steps <= 4096", who, T);
+    NGP_REQUIRE(!null_refusal, "%s", null_refusal);
+    w = nf_layout(c->B, T, workspace);
+    if (!workspace || workspace_bytes < w.total)
+        return ngp_fail(NGP_EWORKSPACE, "%s: workspace of %zu bytes, needs ngp_filter_workspace(B, num_steps) = %zu", who, workspace_bytes, w.total);
+    const int rc_f = ngp_nav_run_forward(field, prepared, w.rays_o, w.rays_d, w.nears, w.fars, 0, T, c->aabb, c->bg, w.image, w.depth, w.weights_sum, w.saved,
+                                         w.saved_bytes, stream);
+    if (rc_f != NGP_OK) return rc_f;
+    A = {};
+    for (int k = 0; k < 12; k++) A.start[k] = c->start_state[k];
+    for (int k = 0; k < 144; k++) A.sig_inv[k] = c->sig_inv[k];
+    return NGP_OK;
+}
+
+static int nf_launched(const char* who, const char* what) {
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? NGP_OK : ngp_fail(NGP_ELAUNCH, "%s: %s: %s", who, what, hipGetErrorString(e));
+}
+
+// the measurement pass at `state` for one batch: rays -> run forward -> loss -> run backward, queued; leaves grad_rays_o, grad_rays_d and the loss partials in w
+static int nf_measure(const char* who, const ngp_nav_field_t* field, const void* prepared, const ngp_filter_cfg_t* c, const nf_view& V, const nf_ws& w,
+                      const float* state, const float* target, const int32_t* batch, void* stream) {
+    const uint32_t B = c->B, T = c->num_steps, blocks = ngp_div_up(B, NF_THREADS);
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_filter_rays, dim3(blocks), dim3(NF_THREADS), 0, s, V, state, batch, B, w.rays_o, w.rays_d, w.nears, w.fars);
+    int rc = nf_launched(who, "rays");
+    if (rc != NGP_OK) return rc;
+    rc = ngp_nav_run_forward(field, prepared, w.rays_o, w.rays_d, w.nears, w.fars, B, T, c->aabb, c->bg, w.image, w.depth, w.weights_sum, w.saved,
+                             w.saved_bytes, stream);
+    if (rc != NGP_OK) return rc;
+    hipLaunchKernelGGL(k_filter_loss, dim3(blocks), dim3(NF_THREADS), 0, s, (const float*)w.image, target, batch, B, c->H, c->W, w.grad_image, w.partials);
+    rc = nf_launched(who, "loss");
+    if (rc != NGP_OK) return rc;
+    return ngp_nav_run_backward(field, prepared, w.rays_o, w.rays_d, w.nears, w.fars, B, T, c->aabb, c->bg, w.grad_image, nullptr, nullptr, w.saved,
+                                w.saved_bytes, w.grad_rays_o, w.grad_rays_d, stream);
+}
+
 extern "C" int ngp_filter_iterations(const ngp_nav_field_t* field, const void* prepared, const ngp_filter_cfg_t* c, float* state, float* adam_state,
                                      const float* target, const int32_t* batches, uint32_t first_iter, uint32_t n_iter, int update, float* losses,
                                      float* states_out, float* grads_out, void* workspace, size_t workspace_bytes, void* stream) {
     nf_view V;
-    const int rc_v = nf_view_of("filter_iterations", c, V);
-    if (rc_v != NGP_OK) return rc_v;
-    const uint32_t B = c->B, T = c->num_steps;
-    NGP_REQUIRE(T >= 1 && T <= NF_MAX_T, "filter_iterations: num_steps = %u; supported 1 <= num_steps <= 4096", T);
-    NGP_REQUIRE(state && adam_state && target && batches, "filter_iterations: null state / adam_state / target / batches");
-    const nf_ws w = nf_layout(B, T, workspace);
-    if (!workspace || workspace_bytes < w.total)
-        return ngp_fail(NGP_EWORKSPACE, "filter_iterations: workspace of %zu bytes, needs ngp_filter_workspace(B, num_steps) = %zu", workspace_bytes, w.total);
-    {   // the field is checked here, before anything is queued (N = 0 validates and launches nothing)
-        const int rc_f = ngp_nav_run_forward(field, prepared, w.rays_o, w.rays_d, w.nears, w.fars, 0, T, c->aabb, c->bg, w.image, w.depth, w.weights_sum,
-                                             w.saved, w.saved_bytes, stream);
-        if (rc_f != NGP_OK) return rc_f;
-    }
-    if (n_iter == 0) return NGP_OK;
+    nf_ws w;
     nf_step_args A;
-    for (int k = 0; k < 12; k++) A.start[k] = c->start_state[k];
-    for (int k = 0; k < 144; k++) A.sig_inv[k] = c->sig_inv[k];
-    A.lr = (float)c->lr; A.beta1 = (float)c->beta1; A.beta2 = (float)c->beta2;
-    A.w1 = (float)(1.0 - c->beta1); A.w2 = (float)(1.0 - c->beta2); A.eps = (float)c->eps;
-    const uint32_t blocks = ngp_div_up(B, NF_THREADS);
-    hipStream_t s = (hipStream_t)stream;
+    int rc = nf_begin("filter_iterations", state && adam_state && target && batches ? nullptr : "filter_iterations: null state / adam_state / target / batches",
+                      field, prepared, c, workspace, workspace_bytes, stream, V, w, A);
+    if (rc != NGP_OK) return rc;
+    A.adam = ngp_adam_fill(c->lr, c->beta1, c->beta2, c->eps);
+    const uint32_t B = c->B, blocks = ngp_div_up(B, NF_THREADS);
     for (uint32_t k = 0; k < n_iter; k++) {
         const int32_t* batch = batches + 2 * (size_t)B * ((size_t)first_iter + k);
-        hipLaunchKernelGGL(k_filter_rays, dim3(blocks), dim3(NF_THREADS), 0, s, V, (const float*)state, batch, B, w.rays_o, w.rays_d, w.nears, w.fars);
-        NGP_CHECK_LAUNCH("filter_iterations: rays");
-        int rc = ngp_nav_run_forward(field, prepared, w.rays_o, w.rays_d, w.nears, w.fars, B, T, c->aabb, c->bg, w.image, w.depth, w.weights_sum, w.saved,
-                                     w.saved_bytes, stream);
+        rc = nf_measure("filter_iterations", field, prepared, c, V, w, state, target, batch, stream);
         if (rc != NGP_OK) return rc;
-        hipLaunchKernelGGL(k_filter_loss, dim3(blocks), dim3(NF_THREADS), 0, s, (const float*)w.image, target, batch, B, c->H, c->W, w.grad_image, w.partials);
-        NGP_CHECK_LAUNCH("filter_iterations: loss");
-        rc = ngp_nav_run_backward(field, prepared, w.rays_o, w.rays_d, w.nears, w.fars, B, T, c->aabb, c->bg, w.grad_image, nullptr, nullptr, w.saved,
-                                  w.saved_bytes, w.grad_rays_o, w.grad_rays_d, stream);
-        if (rc != NGP_OK) return rc;
-        hipLaunchKernelGGL(k_filter_step, dim3(1), dim3(NF_THREADS), 0, s, V, A, update, state, adam_state, batch, B, (const float*)w.grad_rays_o,
-                           (const float*)w.grad_rays_d, (const float*)w.partials, blocks, losses ? losses + k : (float*)nullptr,
+        hipLaunchKernelGGL(k_filter_step, dim3(1), dim3(NF_THREADS), 0, (hipStream_t)stream, V, A, update, state, adam_state, batch, B,
+                           (const float*)w.grad_rays_o, (const float*)w.grad_rays_d, (const float*)w.partials, blocks, losses ? losses + k : (float*)nullptr,
                            states_out ? states_out + 12 * (size_t)k : (float*)nullptr, grads_out ? grads_out + 12 * (size_t)k : (float*)nullptr);
         NGP_CHECK_LAUNCH("filter_iterations: step");
     }
@@ -396,13 +423,12 @@ extern "C" int ngp_filter_iterations(const ngp_nav_field_t* field, const void* p
 // the rest of the estimator's time step (Estimator.estimate_state, nav/estimator_helpers.py:347-406; DESIGN.md §3.5 "Native time step"):
 //
 //   k_filter_propagate   Agent.drone_dynamics, its 12 x 12 Jacobian A (lane j carries the forward-mode tangent along state[j]) and (A sig) A^T + Q
-//   k_filter_hessian     measurement_fn's 12 x 12 Hessian under the reference's differentiation rule: the sums of k_filter_step in its order (the
+//   k_filter_hessian     measurement_fn's 12 x 12 Hessian under the reference's differentiation rule: k_filter_step's passes (nf_ray_sums .. nf_loss: the
 //                        gradient, the loss and dL/dP come out bit for bit as an update = 0 iteration writes them), then sum_ab (dL/dP)_ab d2 P_ab / dr_i dr_j
 //                        into H[6:9, 6:9] (one lane per (i, j), second-order forward mode) and Sinv + Sinv^T everywhere
 //
 // Both evaluate the formulas as written in float64 from the float32 inputs and round every output once (ngp_filter_step.h); one workgroup each.
 // ---------------------------------------------------------------------------
-#include "ngp_filter_step.h"
 
 __global__ __launch_bounds__(NF_THREADS) void k_filter_propagate(nfs_dyn D, const float* __restrict__ state, const float* __restrict__ action,
                                                                  const float* __restrict__ sig, const float* __restrict__ Q,
@@ -446,108 +472,36 @@ __global__ __launch_bounds__(NF_THREADS) void k_filter_hessian(nf_view V, nf_ste
                                                                uint32_t B, const float* __restrict__ grad_rays_o, const float* __restrict__ grad_rays_d,
                                                                const float* __restrict__ partials, uint32_t n_partials, float* __restrict__ hessian,
                                                                float* __restrict__ grad_out, float* __restrict__ loss_out, float* __restrict__ dLdP_out) {
-    __shared__ float sums[NF_WAVES][NF_SUMS];
-    __shared__ float x[12], delta[12], g_image[12], quad[12], mse;
+    __shared__ nf_shared S;
     __shared__ double h_image[9];
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    if (tid < 12) {
-        const float s = state[tid];
-        x[tid] = s;
-        delta[tid] = s - A.start[tid];
-    }
-    // k_filter_step's sums, in its order
-    float acc[NF_SUMS];
-#pragma unroll
-    for (int k = 0; k < (int)NF_SUMS; k++) acc[k] = 0.0f;
-    ngp_camera unit;
-#pragma unroll
-    for (int e = 0; e < 9; e++) unit.r[e] = e % 4 == 0 ? 1.0f : 0.0f;
-    unit.t[0] = unit.t[1] = unit.t[2] = 0.0f;
-    unit.fx = V.fx; unit.fy = V.fy; unit.cx = V.cx; unit.cy = V.cy; unit.W = V.W; unit.H = V.H;
-    for (uint32_t n = tid; n < B; n += NF_THREADS) {
-        uint32_t row, col;
-        nf_pixel(batch, n, V.H, V.W, row, col);
-        float dir[3];
-        ngp_camera_ray(unit, row * V.W + col, dir);
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-            acc[k] += grad_rays_o[3 * (size_t)n + k];
-            const float g = grad_rays_d[3 * (size_t)n + k];
-#pragma unroll
-            for (int j = 0; j < 3; j++) acc[3 + 3 * k + j] += g * dir[j];
-        }
-    }
-    for (uint32_t i = tid; i < n_partials; i += NF_THREADS) acc[12] += partials[i];
-#pragma unroll
-    for (int k = 0; k < (int)NF_SUMS; k++) acc[k] = nf_wave_sum(acc[k]);
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < (int)NF_SUMS; k++) sums[wave][k] = acc[k];
-    }
+    const uint32_t tid = threadIdx.x;
+    nf_load_state(S, A, state);
+    nf_ray_sums(S, V, batch, B, grad_rays_o, grad_rays_d, partials, n_partials);
     __syncthreads();
     if (tid == 0) {
         float tot[NF_SUMS];
-#pragma unroll
-        for (int k = 0; k < (int)NF_SUMS; k++) {
-            float s = sums[0][k];
-#pragma unroll
-            for (uint32_t w = 1; w < NF_WAVES; w++) s += sums[w][k];
-            tot[k] = s;
-        }
-        float xs[12];
-#pragma unroll
-        for (int k = 0; k < 12; k++) { xs[k] = x[k]; g_image[k] = 0.0f; }
-        nf_rodrigues Q;
-        float P[9], T[3], gr[3];
-        nf_pose(xs, Q, P, T);
-        nf_pose_backward(xs + 6, Q, tot + 3, gr);
-#pragma unroll
-        for (int i = 0; i < 3; i++) {
-            g_image[(i + 1) % 3] = tot[i];
-            g_image[6 + i] = gr[i];
-        }
-        mse = tot[12] / (float)(3ull * B);
+        nf_image_gradient(S, B, tot);
         if (dLdP_out) {
 #pragma unroll
             for (int e = 0; e < 9; e++) dLdP_out[e] = tot[3 + e];
         }
     }
-    // the second wave meanwhile: lane 3 i + j takes d2 / dr_i dr_j of the camera rotation and contracts it with dL/dP (the same sums, added in the same order)
+    // the second wave meanwhile: lane 3 i + j takes d2 / dr_i dr_j of the camera rotation and contracts it with dL/dP (the same totals, nf_total's order)
     if (tid >= 64 && tid < 73) {
         const int ij = (int)tid - 64, i = ij / 3, j = ij % 3;
         nfs_d2 r[3], P[9];
 #pragma unroll
-        for (int k = 0; k < 3; k++) r[k] = nfs_d2((double)x[6 + k], k == i ? 1.0 : 0.0, k == j ? 1.0 : 0.0, 0.0);
+        for (int k = 0; k < 3; k++) r[k] = nfs_d2((double)S.x[6 + k], k == i ? 1.0 : 0.0, k == j ? 1.0 : 0.0, 0.0);
         nfs_measurement_rotation(r, (double)1e-10f, (double)NF_C90, P);
         double h = 0.0;
 #pragma unroll
-        for (int e = 0; e < 9; e++) {
-            float s = sums[0][3 + e];
-#pragma unroll
-            for (uint32_t w = 1; w < NF_WAVES; w++) s += sums[w][3 + e];
-            h += (double)s * P[e].ab;
-        }
+        for (int e = 0; e < 9; e++) h += (double)nf_total(S, 3 + e) * P[e].ab;
         h_image[ij] = h;
     }
-    double mg = 0.0;
-    if (tid < 12) {
-        double row = 0.0;
-#pragma unroll
-        for (int j = 0; j < 12; j++) {
-            const double dj = (double)delta[j];
-            row += (double)A.sig_inv[tid * 12 + j] * dj;
-            mg += ((double)A.sig_inv[tid * 12 + j] + (double)A.sig_inv[j * 12 + tid]) * dj;
-        }
-        quad[tid] = (float)((double)delta[tid] * row);
-    }
+    const double mg = nf_process_row(S, A);
     __syncthreads();
-    if (tid < 12 && grad_out) grad_out[tid] = g_image[tid] + (float)mg;
-    if (tid == 0 && loss_out) {
-        float process = quad[0];
-#pragma unroll
-        for (int k = 1; k < 12; k++) process += quad[k];
-        *loss_out = mse + process;
-    }
+    if (tid < 12 && grad_out) grad_out[tid] = S.g_image[tid] + (float)mg;
+    if (tid == 0 && loss_out) *loss_out = nf_loss(S);
     if (tid < 144) {
         const uint32_t i = tid / 12, j = tid % 12;
         double h = (double)A.sig_inv[i * 12 + j] + (double)A.sig_inv[j * 12 + i];
@@ -574,36 +528,15 @@ extern "C" int ngp_filter_hessian(const ngp_nav_field_t* field, const void* prep
                                   const int32_t* batch, float* hessian, float* grad, float* loss, float* dLdP, void* workspace, size_t workspace_bytes,
                                   void* stream) {
     nf_view V;
-    const int rc_v = nf_view_of("filter_hessian", c, V);
-    if (rc_v != NGP_OK) return rc_v;
-    const uint32_t B = c->B, T = c->num_steps;
-    NGP_REQUIRE(T >= 1 && T <= NF_MAX_T, "filter_hessian: num_steps = %u; supported 1 <= num_steps <= 4096", T);
-    NGP_REQUIRE(state && target && batch && hessian, "filter_hessian: null state / target / batch / hessian");
-    const nf_ws w = nf_layout(B, T, workspace);
-    if (!workspace || workspace_bytes < w.total)
-        return ngp_fail(NGP_EWORKSPACE, "filter_hessian: workspace of %zu bytes, needs ngp_filter_workspace(B, num_steps) = %zu", workspace_bytes, w.total);
-    {   // the field is checked here, before anything is queued (N = 0 validates and launches nothing)
-        const int rc_f = ngp_nav_run_forward(field, prepared, w.rays_o, w.rays_d, w.nears, w.fars, 0, T, c->aabb, c->bg, w.image, w.depth, w.weights_sum,
-                                             w.saved, w.saved_bytes, stream);
-        if (rc_f != NGP_OK) return rc_f;
-    }
-    nf_step_args A = {};
-    for (int k = 0; k < 12; k++) A.start[k] = c->start_state[k];
-    for (int k = 0; k < 144; k++) A.sig_inv[k] = c->sig_inv[k];
-    const uint32_t blocks = ngp_div_up(B, NF_THREADS);
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_filter_rays, dim3(blocks), dim3(NF_THREADS), 0, s, V, state, batch, B, w.rays_o, w.rays_d, w.nears, w.fars);
-    NGP_CHECK_LAUNCH("filter_hessian: rays");
-    int rc = ngp_nav_run_forward(field, prepared, w.rays_o, w.rays_d, w.nears, w.fars, B, T, c->aabb, c->bg, w.image, w.depth, w.weights_sum, w.saved,
-                                 w.saved_bytes, stream);
+    nf_ws w;
+    nf_step_args A;
+    int rc = nf_begin("filter_hessian", state && target && batch && hessian ? nullptr : "filter_hessian: null state / target / batch / hessian", field,
+                      prepared, c, workspace, workspace_bytes, stream, V, w, A);
     if (rc != NGP_OK) return rc;
-    hipLaunchKernelGGL(k_filter_loss, dim3(blocks), dim3(NF_THREADS), 0, s, (const float*)w.image, target, batch, B, c->H, c->W, w.grad_image, w.partials);
-    NGP_CHECK_LAUNCH("filter_hessian: loss");
-    rc = ngp_nav_run_backward(field, prepared, w.rays_o, w.rays_d, w.nears, w.fars, B, T, c->aabb, c->bg, w.grad_image, nullptr, nullptr, w.saved,
-                              w.saved_bytes, w.grad_rays_o, w.grad_rays_d, stream);
+    rc = nf_measure("filter_hessian", field, prepared, c, V, w, state, target, batch, stream);
     if (rc != NGP_OK) return rc;
-    hipLaunchKernelGGL(k_filter_hessian, dim3(1), dim3(NF_THREADS), 0, s, V, A, state, batch, B, (const float*)w.grad_rays_o, (const float*)w.grad_rays_d,
-                       (const float*)w.partials, blocks, hessian, grad, loss, dLdP);
+    hipLaunchKernelGGL(k_filter_hessian, dim3(1), dim3(NF_THREADS), 0, (hipStream_t)stream, V, A, state, batch, c->B, (const float*)w.grad_rays_o,
+                       (const float*)w.grad_rays_d, (const float*)w.partials, ngp_div_up(c->B, NF_THREADS), hessian, grad, loss, dLdP);
     NGP_CHECK_LAUNCH("filter_hessian: hessian");
     return NGP_OK;
 }

@@ -15,8 +15,7 @@
 // contracts it with the adjoints.  The derivative conventions are torch autograd's (nav/math_utils.py:115-156): the linearised acos with
 // its float32 slope, the 1 / (2 sin(ang + 1e-10)) factor, no gradient through a zero angle, zero gradient of the norm of a zero vector.
 // No atomics; every sum runs in a fixed order, so two runs are bit-identical.
-#include "ngp_device.h"
-
+#include "ngp_nav_step.h"
 
 #define NP_HD __host__ __device__ __forceinline__
 
@@ -39,7 +38,7 @@ struct np_args {
     int32_t fade_out_epoch;
     float fade_out_sharpness;
     float acos_lim, acos_eps, acos_slope;           // (float)(1 - 1e-7), (float)1e-7, (float)(arccos(1 - 1e-7) / 1e-7) in float64
-    float lr, beta1, beta2, w1, w2, eps;            // Adam: w1 = (float)(1 - beta1), w2 = (float)(1 - beta2) formed in float64
+    ngp_adam_coef adam;
 };
 
 NP_HD void np_cross(const float* a, const float* b, float* o) {
@@ -379,18 +378,6 @@ NP_HD float np_tangent(const np_args& A, const float* rows, uint32_t p) {
     return grad;
 }
 
-// one element of torch.optim.Adam(capturable=True)'s multi-tensor step (torch/optim/adam.py, _multi_tensor_adam), step = the new count
-NP_HD float np_adam(const np_args& A, float param, float grad, float* m, float* v, float step) {
-    *m = *m + A.w1 * (grad - *m);                                        // lerp(exp_avg, grad, 1 - beta1)
-    *v = *v * A.beta2 + A.w2 * (grad * grad);                            // mul + addcmul
-    float bc1 = powf(A.beta1, step), bc2 = powf(A.beta2, step);
-    bc1 = bc1 - 1.0f; bc2 = -(bc2 - 1.0f);
-    const float step_size = 1.0f / (bc1 / A.lr);
-    const float bc2_sqrt = sqrtf(bc2);
-    const float denom = (sqrtf(*v) / bc2_sqrt + A.eps) / step_size;
-    return param + *m / denom;
-}
-
 // ---------------------------------------------------------------------------
 // device
 // ---------------------------------------------------------------------------
@@ -432,12 +419,6 @@ __global__ __launch_bounds__(NP_K1_THREADS) void k_plan_kinematics(np_args A, co
         for (uint32_t e = tid; e < 3 * A.S * A.B; e += NT) points[e] = np_point(A, rows, body, e);
 }
 
-__device__ __forceinline__ float np_wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 __global__ __launch_bounds__(NP_K3_THREADS) void k_plan_cost_step(np_args Aarg, uint32_t epoch, int update, float* __restrict__ states,
                                                                   float* __restrict__ ia, float* __restrict__ adam, const float* __restrict__ body,
                                                                   const float* __restrict__ sigma, const float* __restrict__ jac,
@@ -471,12 +452,12 @@ __global__ __launch_bounds__(NP_K3_THREADS) void k_plan_cost_step(np_args Aarg, 
                 for (int m = 0; m < 3; m++) gr[a * 3 + m] += q[a] * bb[m];
             }
         }
-        sc = np_wave_sum(sc);
-        s2 = np_wave_sum(s2);
+        sc = ngp_wave_sum(sc);
+        s2 = ngp_wave_sum(s2);
 #pragma unroll
-        for (int a = 0; a < 3; a++) gp[a] = np_wave_sum(gp[a]);
+        for (int a = 0; a < 3; a++) gp[a] = ngp_wave_sum(gp[a]);
 #pragma unroll
-        for (int k = 0; k < 9; k++) gr[k] = np_wave_sum(gr[k]);
+        for (int k = 0; k < 9; k++) gr[k] = ngp_wave_sum(gr[k]);
         if (lane == 0) {
             r[F_COLL] = sc;
             r[F_ASP] = s2;
@@ -505,7 +486,7 @@ __global__ __launch_bounds__(NP_K3_THREADS) void k_plan_cost_step(np_args Aarg, 
         if (update) {
             float* param = p < 2 ? ia + p : states + (p - 2);
             float m = adam[p], v = adam[P + p];
-            *param = np_adam(A, *param, g, &m, &v, step);
+            *param = ngp_adam_step(A.adam, *param, g, &m, &v, step);
             adam[p] = m;
             adam[P + p] = v;
         }
@@ -544,8 +525,7 @@ static int np_fill(const char* who, const ngp_plan_cfg_t* c, uint32_t R, uint32_
     A.acos_lim = (float)(1.0 - eps);
     A.acos_eps = (float)eps;
     A.acos_slope = (float)(acos(1.0 - eps) / eps);
-    A.lr = (float)c->lr; A.beta1 = (float)c->beta1; A.beta2 = (float)c->beta2;
-    A.w1 = (float)(1.0 - c->beta1); A.w2 = (float)(1.0 - c->beta2); A.eps = (float)c->eps;
+    A.adam = ngp_adam_fill(c->lr, c->beta1, c->beta2, c->eps);
     return NGP_OK;
 }
 

@@ -90,11 +90,10 @@ template <class T> NFS_HD void nfs_vec_to_rot(const T* r, double tiny, T* R) {
     for (int e = 0; e < 9; e++) R[e] = (T(e % 4 == 0 ? 1.0 : 0.0) + sn * K[e]) + MK[e];
 }
 
-// measurement_fn's camera rotation (nav/estimator_helpers.py:301-309): P = cycle (rot_x(pi/2) R(r)) diag(1, -1, -1); c90 is the reference's float32
-// cos((float)(pi / 2)), its sine is 1
-template <class T> NFS_HD void nfs_measurement_rotation(const T* r, double tiny, double c90, T* P) {
-    T R[9], Rb[9];
-    nfs_vec_to_rot(r, tiny, R);
+// the axis part of measurement_fn's camera rotation (nav/estimator_helpers.py:301-309): P = cycle (rot_x(pi/2) R) diag(1, -1, -1); c90 is the reference's
+// float32 cos((float)(pi / 2)), its sine is 1.  T = float is the filter's own pose chain (nav_filter.hip nf_pose)
+template <class T> NFS_HD void nfs_camera_axes(const T* R, double c90, T* P) {
+    T Rb[9];
 #pragma unroll
     for (int j = 0; j < 3; j++) {
         Rb[0 + j] = R[0 + j];
@@ -106,6 +105,12 @@ template <class T> NFS_HD void nfs_measurement_rotation(const T* r, double tiny,
         const int m = (i + 1) % 3;
         P[i * 3 + 0] = Rb[m * 3 + 0]; P[i * 3 + 1] = -Rb[m * 3 + 1]; P[i * 3 + 2] = -Rb[m * 3 + 2];
     }
+}
+// measurement_fn's camera rotation as a function of the rotation vector, over forward-mode numbers
+template <class T> NFS_HD void nfs_measurement_rotation(const T* r, double tiny, double c90, T* P) {
+    T R[9];
+    nfs_vec_to_rot(r, tiny, R);
+    nfs_camera_axes(R, c90, P);
 }
 
 // Agent's cfg in double, with what the host prepares once: I^-1 (adjugate) and acos_safe's constants, eps = 1e-7, edge = acos(1 - eps), slope = edge / eps
