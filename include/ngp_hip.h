@@ -659,8 +659,29 @@ int ngp_plan_epochs(const ngp_nav_field_t* field_host, const void* prepared, con
                     uint32_t first_epoch, uint32_t n_epochs, int update, float* losses, float* per_state,
                     void* workspace, size_t workspace_bytes, void* stream);
 
+/* The planner's A* initialisation (Planner.a_star_init, nav/quad_plot.py:64-115; csrc/nav_astar.hip, DESIGN.md §3.5 "Native A* initialisation").
+ *
+ * Occupancy: density_fn over the lattice axis_x x axis_y x axis_z (device float32 [side] each), MaxPool3d(kernel) and `> threshold` in one launch.
+ * occupied: device uint8 [G,G,G], G = side / kernel (floor: lattice points past G * kernel are ignored, as MaxPool3d ignores them), x slowest.
+ * rot9_host: simulate.py:340's axis change as 9 row-major host floats, or NULL.  Every point's sigma is bit for bit what the forward density query
+ * above gives for it, so `occupied` equals the unfused route's bit for bit; the side^3 sigma lattice is never written.
+ * NGP_EINVAL, nothing launched: null pointers, kernel == 0, side < kernel, side > 1024, a field the nav queries refuse. */
+int ngp_plan_occupancy(const ngp_nav_field_t* field_host, const void* prepared, const float* axis_x, const float* axis_y, const float* axis_z,
+                       uint32_t side, uint32_t kernel, const float* rot9_host /* or NULL */, float threshold, uint8_t* occupied, void* stream);
+/* The search, one launch of one workgroup: occupied device uint8 [dims 0,1,2] (non-zero = occupied), start and goal cells (host).
+ * path: device int32 [cap,3], the cells start -> goal; result: device int32 [2] = {status, n_cells}, always written.
+ *   status 0 ok (n_cells rows of path written) | 1 start occupied | 2 goal occupied | 3 no path | 4 the path has n_cells > cap cells (none written)
+ * The path is a shortest 6-connected path, so it has the length of the reference's astar (nav/quad_helpers.py:201-258); among equally short ones
+ * it is the one that from every cell moves to the FIRST neighbour in the order +x, -x, +y, -y, +z, -z that is one step closer to the goal.
+ * NGP_EINVAL, nothing launched: null pointers, a zero dim, more than 27000 cells (30^3), start or goal outside the grid, cap == 0. */
+int ngp_plan_astar(const uint8_t* occupied, const uint32_t dims_host[3], const int32_t start_host[3], const int32_t goal_host[3],
+                   int32_t* path, uint32_t cap, int32_t* result, void* stream);
+/* The same search evaluated on the host by the functions the kernel calls (csrc/ngp_plan_path.h), for tests: all pointers host memory. */
+int ngp_plan_astar_host(const uint8_t* occupied, const uint32_t dims_host[3], const int32_t start_host[3], const int32_t goal_host[3],
+                        int32_t* path, uint32_t cap, int32_t* result);
+
 /* ------------------------------------------------------------------------ */
-/* Pose filter  (reference: Estimator.estimate_relative_pose / measurement_fn, */
+/* Pose filter (reference: Estimator.estimate_relative_pose / measurement_fn, */
 /* nav/estimator_helpers.py:173-327; csrc/nav_filter.hip, DESIGN.md §3.5 "Native pose filter") */
 /* ------------------------------------------------------------------------ */
 

@@ -386,17 +386,39 @@ def _reduced_state(state):
     return torch.cat([state[:3], torch.atan2(R[1, 0], R[0, 0])[None]]).detach()
 
 
-class NativePlanner:
-    """Planner (nav/quad_plot.py) with its optimisation loop native: calc_everything -> body_to_world -> get_state_cost -> total_cost ->
-    backward -> Adam run as ngp_plan_epochs, i.e. per epoch one launch of the kinematics, one of the density query (NativeNavQueries'
-    value-and-Jacobian kernel, simulate.py:340's axis change folded in) and one of cost, gradient and Adam step.  Same cfg keys, the same
-    semantics as the reference's methods; the loss history is a device tensor (`losses`) instead of a print per epoch.
+def astar_states(path, grid_size, lo, hi, noise=None):
+    """The states Planner.a_star_init makes of a path of cells (nav/quad_plot.py:97-113), in its float32 op order: cell -> lo + (hi - lo) * (cell / grid_size)
+    (for the box [-1, 1]^3 bit for bit the reference's 2 * (path / grid_size) - 1), a zero heading column, `+ noise` ([n,4] or None), then the three-point
+    smoothing (prev + next + states) / 3 with the end rows repeated.  path: integer [n,3]; plain torch, on path's device."""
+    dev = path.device
+    lo = torch.as_tensor(lo, dtype=torch.float32).to(dev)
+    hi = torch.as_tensor(hi, dtype=torch.float32).to(dev)
+    squares = lo + (hi - lo) * (path.to(torch.float32) / grid_size)
+    states = torch.cat([squares, torch.zeros((squares.shape[0], 1), dtype=torch.float32, device=dev)], dim=-1)
+    if noise is not None:
+        states = states + noise.to(dev, torch.float32)
+    prev_smooth = torch.cat([states[0, None, :], states[:-1, :]], dim=0)
+    next_smooth = torch.cat([states[1:, :], states[-1, None, :]], dim=0)
+    return (prev_smooth + next_smooth + states) / 3
 
-        traj.a_star_init()
-        plan = NativePlanner.from_planner(traj, queries)      # queries: NativeNavQueries
+
+class NativePlanner:
+    """Planner (nav/quad_plot.py) native from its first step.  `a_star_init` builds the occupancy lattice (density query, max-pool and threshold in one
+    launch), searches it on the device and turns the path into the states; `learn_init` / `learn_update` run calc_everything -> body_to_world ->
+    get_state_cost -> total_cost -> backward -> Adam as ngp_plan_epochs, i.e. per epoch one launch of the kinematics, one of the density query
+    (NativeNavQueries' value-and-Jacobian kernel, simulate.py:340's axis change folded in) and one of cost, gradient and Adam step.  Same cfg keys, the
+    same semantics as the reference's methods; the loss history is a device tensor (`losses`) instead of a print per epoch.
+
+        plan = NativePlanner(start, end, cfg, queries)        # queries: NativeNavQueries
+        plan.a_star_init()
         plan.learn_init()
+
+    The path a_star_init finds has the length of the reference's; among equally short paths it is chosen by a rule of its own (csrc/ngp_plan_path.h,
+    DESIGN 3.5).  `from_planner` remains for adopting a reference Planner's own path after its a_star_init().
     """
     SAVE_STEP = 50                                          # learn_init / learn_update save every 50th epoch when `basefolder` is set
+    MIN_R, MAX_R = 2, 255                                   # csrc/nav_plan.hip: NP_MIN_R, NP_MAX_R
+    MAX_CELLS = 27000                                       # csrc/ngp_plan_path.h: NGP_PLAN_MAX_CELLS
 
     def __init__(self, start_state, end_state, cfg, queries):
         self._bind(queries)
@@ -439,6 +461,82 @@ class NativePlanner:
         planner.start_state = self.start_state
         planner.epoch = self.epoch
         return planner
+
+    # -- the A* initialisation (csrc/nav_astar.hip) --------------------------------------------------------------------
+    PATH_ERRORS = {1: "the start cell {start} is occupied", 2: "the goal cell {goal} is occupied",
+                   3: "Failed to find path from cell {start} to cell {goal}!"}
+
+    def occupancy(self, side=100, kernel_size=5, threshold=0.3, lo=(-1., -1., -1.), hi=(1., 1., 1.)):
+        """a_star_init's `occupied` (nav/quad_plot.py:65-84): density_fn over the lattice linspace(lo, hi, side)^3, MaxPool3d(kernel_size) and `> threshold`
+        in one launch -> uint8 [G,G,G] on the device, G = side // kernel_size, indexed (x, y, z).  Bit for bit the unfused route's."""
+        import ctypes
+        import ngp_hip as _hip
+        side, kernel_size = int(side), int(kernel_size)
+        if kernel_size < 1 or side < kernel_size:
+            raise ValueError(f"occupancy: side = {side}, kernel_size = {kernel_size}: need 1 <= kernel_size <= side")
+        G = side // kernel_size
+        axes = [torch.linspace(float(lo[k]), float(hi[k]), side, dtype=torch.float32).to(self.device) for k in range(3)]     # the reference's lattice, bit for bit
+        occupied = torch.empty((G, G, G), dtype=torch.uint8, device=self.device)
+        st, prep = self.queries.native.struct()
+        rot = (ctypes.c_float * 9)(*NativeNavQueries._ROT9)
+        _hip.check(_hip.lib().ngp_plan_occupancy(ctypes.byref(st), _hip.ptr(prep), _hip.ptr(axes[0]), _hip.ptr(axes[1]), _hip.ptr(axes[2]), side, kernel_size,
+                                                 rot, float(threshold), _hip.ptr(occupied), _hip.stream()), "plan_occupancy")
+        return occupied
+
+    def find_path(self, occupied, start, goal):
+        """astar (nav/quad_helpers.py:201-258) on the device: occupied [gx,gy,gz] (non-zero = occupied), start / goal cells -> the path start -> goal as an
+        int32 [n,3] device tensor.  A shortest path, of the reference's length; among equal ones the first-neighbour rule of csrc/ngp_plan_path.h decides.
+        One host read (status, n and the cells: n is data).  ValueError: start occupied, goal occupied (the reference asserts), no path (the reference's
+        "Failed to find path!"), a cell outside the grid."""
+        import ctypes
+        import ngp_hip as _hip
+        if occupied.dim() != 3 or not occupied.is_cuda:
+            raise ValueError("find_path: occupied must be a [gx,gy,gz] tensor on the GPU")
+        occ = occupied.contiguous() if occupied.dtype == torch.uint8 else (occupied != 0).to(torch.uint8).contiguous()
+        dims = tuple(int(v) for v in occ.shape)
+        start, goal = tuple(int(v) for v in start), tuple(int(v) for v in goal)
+        for name, cell in (("start", start), ("goal", goal)):
+            if len(cell) != 3 or any(c < 0 or c >= d for c, d in zip(cell, dims)):
+                raise ValueError(f"find_path: the {name} cell {cell} is outside the grid {dims}")
+        cells = dims[0] * dims[1] * dims[2]
+        if cells < 1 or cells > self.MAX_CELLS:
+            raise ValueError(f"find_path: a grid of {dims} has {cells} cells; supported 1 .. {self.MAX_CELLS} (30^3)")
+        buf = torch.empty(2 + 3 * cells, dtype=torch.int32, device=occ.device)          # result [2] | path [cells, 3]: no path has more cells than the grid
+        _hip.check(_hip.lib().ngp_plan_astar(_hip.ptr(occ), (ctypes.c_uint32 * 3)(*dims), (ctypes.c_int32 * 3)(*start), (ctypes.c_int32 * 3)(*goal),
+                                             _hip.ptr(buf[2:]), cells, _hip.ptr(buf), _hip.stream()), "plan_astar")
+        status, n = (int(v) for v in buf[:2].cpu().tolist())                             # the one host read
+        if status in self.PATH_ERRORS:
+            raise ValueError("find_path: " + self.PATH_ERRORS[status].format(start=start, goal=goal))
+        if status != 0:
+            raise RuntimeError(f"find_path: status {status} with {n} cells of {cells}")
+        return buf[2:2 + 3 * n].view(n, 3).clone()
+
+    def _grid_cell(self, state, G, lo, hi):
+        """a_star_init's cell of a position (nav/quad_plot.py:89-92): int(G * (pos - lo) / (hi - lo)) per axis, float32 on the CPU in that order"""
+        pos = state[:3].detach().to("cpu", torch.float32)
+        f = G * (pos - torch.as_tensor(lo, dtype=torch.float32)) / (torch.as_tensor(hi, dtype=torch.float32) - torch.as_tensor(lo, dtype=torch.float32))
+        return tuple(int(f[i]) for i in range(3))
+
+    def a_star_init(self, side=100, kernel_size=5, threshold=0.3, lo=(-1., -1., -1.), hi=(1., 1., 1.), noise_std=0.001, generator=None):
+        """Planner.a_star_init (nav/quad_plot.py:64-115): occupancy lattice, path search, path -> states (astar_states); `states` becomes the n rows of the
+        path whatever cfg['steps'] was.  noise_std: the reference's normal(0, 0.001), drawn on the CPU as torch.randn(n, 4, generator=generator) * noise_std
+        so that a seed reproduces on any device; 0 = none.  Keeps `occupied` and `path`; returns the path.  ValueError, `states` untouched: start or goal
+        outside the lattice (before any launch), find_path's, a path of fewer than 2 or more than 255 cells (the epochs' supported R)."""
+        G = int(side) // int(kernel_size) if int(kernel_size) >= 1 else 0
+        start, goal = self._grid_cell(self.start_state, G, lo, hi), self._grid_cell(self.end_state, G, lo, hi)
+        for name, cell in (("start", start), ("goal", goal)):
+            if any(c < 0 or c >= G for c in cell):
+                raise ValueError(f"a_star_init: the {name} state lies in cell {cell}, outside the {G}^3 lattice over {tuple(lo)} .. {tuple(hi)}")
+        occupied = self.occupancy(side, kernel_size, threshold, lo, hi)
+        path = self.find_path(occupied, start, goal)
+        n = int(path.shape[0])
+        if not self.MIN_R <= n <= self.MAX_R:
+            raise ValueError(f"a_star_init: the path from cell {start} to cell {goal} has {n} cells; the planner's epochs support {self.MIN_R} .. {self.MAX_R} states")
+        noise = torch.randn(n, 4, generator=generator) * noise_std if noise_std else None
+        self.states = astar_states(path, G, lo, hi, noise).contiguous()
+        self.occupied, self.path = occupied, path
+        self._ws = None                                     # laid out again for the new R
+        return path
 
     # -- plumbing ------------------------------------------------------------------------------------------------------
     def _bind(self, queries):

@@ -138,6 +138,9 @@ _SIGNATURES = {
     "ngp_plan_workspace": (c_sz, [c_u32, c_u32]),
     "ngp_plan_kinematics": (c_int, [c_vp, c_vp, c_vp, c_u32, c_vp, c_u32, c_vp, c_vp, c_vp, c_vp]),
     "ngp_plan_epochs": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_u32, c_u32, c_u32, c_u32, c_int, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "ngp_plan_occupancy": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_u32, c_u32, c_vp, c_f32, c_vp, c_vp]),
+    "ngp_plan_astar": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_u32, c_vp, c_vp]),
+    "ngp_plan_astar_host": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_u32, c_vp]),
     "ngp_filter_workspace": (c_sz, [c_u32, c_u32]),
     "ngp_filter_iterations": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_u32, c_u32, c_int, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "ngp_filter_rays": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
