@@ -250,6 +250,27 @@ int ngp_grid_scatter_binned_phase_listed(int phase, const void* grad, const floa
                                          uint32_t gridtype, int align_corners, int out_dtype, float out_scale, const uint32_t* list,
                                          const uint32_t* list_count, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The binned scatter for FLOAT32 gradients and a float32 table (D = 3, C = 2, levels of at most 2^19 rows): the table gradient of the default field,
+ * bitwise reproducible.  grad [L][B][2] f32 (level-major), inputs [B,3] f32 in [0,1]; grad_embeddings [sO,2] f32 is WRITTEN WHOLE (no pre-zeroing),
+ * multiplied by out_scale.  Index and weight arithmetic is that of ngp_grid_encode_backward (f32): a contribution is the binary32 product w * g; runs of
+ * consecutive samples in one cell are summed first in binary32 by a fixed tree (at most 6 adds deep) whose shape depends on the input alone.
+ *   Reproducibility: for a given input the output bits do not depend on scheduling.  There is no float atomic, global or on chip: a row's entries are
+ *   added as 64-bit integers in units of 2^(E - K), E the exponent of the largest |entry| of that row and feature, K = 36 (2^25 entries of a pass
+ *   times 2^37 units stay below 2^63), so the sum is a function of the multiset of entries.
+ *   Accuracy: row r, feature f = one binary32 rounding of (the sum of its n_r entries +- n_r * 2^(E_rf - K - 1)).  out_scale != 1 and the value of an
+ *   earlier pass enter in binary64 before that rounding.
+ *   Passes: 2^22 samples each; later passes add into the output in float32, in pass order.
+ *   An inf / NaN contribution makes the elements it reaches NaN (its row and feature, and through the run sums possibly neighbours in the same level);
+ *   other levels stay finite.
+ * workspace: ngp_grid_scatter_binned_f32_workspace(B, L) bytes (80 B per sample and level: 1,280 B per sample at L = 16, at most 5.4 GB), taken from
+ * the caller, contents arbitrary.  B == 0 writes a table of zeros.
+ * Refusals, all before anything reaches the device: null pointers, L outside 1..32, max_level_rows outside 1..2^19 (NGP_EINVAL); a workspace that is
+ * null or too short (NGP_EWORKSPACE). */
+size_t ngp_grid_scatter_binned_f32_workspace(uint32_t B, uint32_t L);
+int ngp_grid_scatter_binned_f32(const float* grad, const float* inputs, const int32_t* offsets, float* grad_embeddings,
+                                uint32_t B, uint32_t L, float S, uint32_t H, uint32_t max_level_rows, uint32_t gridtype,
+                                int align_corners, float out_scale, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------ */
 /* optimiser step of the training loop                                       */
 /* (reference: main_nerf.py:126 torch.optim.Adam(model.get_params(lr), betas=(0.9, 0.99), eps=1e-15); nerf/utils.py:329 GradScaler,       */

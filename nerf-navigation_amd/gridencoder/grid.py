@@ -27,6 +27,10 @@ RECOMPUTE_MIN_POINTS = 32768
 # (ngp_grid_scatter_binned: no global atomics, float32 sums, float32 output = the parameter's dtype, no zero fill, no widening copy).
 # False: the reference's route, half2 atomics into a zero-filled half table (ngp_grid_encode_backward).
 BINNED_SCATTER = True
+# True: the table gradient of a FLOAT32 D = 3, C = 2 grid (the default field without autocast) is summed on chip as well (ngp_grid_scatter_binned_f32:
+# integer adds under a per-row block exponent, no atomics on floats anywhere, no zero fill) -- the same bits on every run.
+# False: the reference's route, float atomics into a zero-filled table (ngp_grid_encode_backward), whose bits depend on the order the atomics arrive in.
+BINNED_SCATTER_F32 = False
 # True: D = 3, C = 2 forwards write [B, L*C] directly (ngp_grid_encode_forward_rows) instead of [L, B, C] + permute copy.  Same bits.
 ROWS_FORWARD = True
 # ... except where the caller says its points are incoherent (`with level_major_forward():`, the occupancy-grid refresh's random points): then the
@@ -148,6 +152,25 @@ def table_gradient_binned(grad, inputs, offsets, B, L, S, H, gridtype, align_cor
     return out
 
 
+def binned_f32_applies(D, C, embeddings, offsets):
+    """whether ngp_grid_scatter_binned_f32 takes this table: D = 3, C = 2, float32, no level beyond 2^19 rows"""
+    return D == 3 and C == 2 and embeddings.dtype == torch.float32 and int(offsets_max_rows(offsets)) <= (1 << 19)
+
+
+def table_gradient_binned_f32(grad, inputs, offsets, B, L, S, H, gridtype, align_corners):
+    """grad [L,B,2] float32 (level-major), inputs [B,3] float32 in [0,1] -> the float32 table gradient [sO,2], summed on chip with integer adds
+    (ngp_grid_scatter_binned_f32): bitwise reproducible, the whole table written by the call.  Shared by _grid_encode.backward and the default
+    field's native training step (ngp/field.py: _field_train_f32)."""
+    lib = _hip.lib()
+    rows, n, _ = offsets_info(offsets)
+    out = torch.empty(n, 2, dtype=torch.float32, device=inputs.device)
+    ws = _hip.workspace(lib.ngp_grid_scatter_binned_f32_workspace(B, L), inputs.device)
+    with _hip.timed("grid_scatter_binned_f32"):
+        _hip.check(lib.ngp_grid_scatter_binned_f32(_hip.ptr(grad), _hip.ptr(inputs), _hip.ptr(offsets), _hip.ptr(out), B, L, float(S), H, rows, gridtype,
+                                                   int(align_corners), 1.0, _hip.ptr(ws), ws.numel(), _hip.stream()), "grid_scatter_binned_f32")
+    return out
+
+
 class _grid_encode(Function):
     """reference: gridencoder/grid.py:19-87"""
 
@@ -216,8 +239,12 @@ class _grid_encode(Function):
             return None, None, None, None, None, None, None, None
         binned = (BINNED_SCATTER and need_table and D == 3 and C == 2 and embeddings.dtype == torch.float16
                   and int(offsets_max_rows(offsets)) <= (1 << 19))
+        binned_f32 = BINNED_SCATTER_F32 and need_table and binned_f32_applies(D, C, embeddings, offsets)
         grad_embeddings = None
-        if need_table:
+        if need_table and binned_f32:
+            grad_embeddings = table_gradient_binned_f32(grad, inputs, offsets, B, L, S, H, gridtype, ctx.align_corners)
+            binned = True                              # the atomic kernel below is then asked for the input gradient only, if at all
+        elif need_table:
             grad_embeddings = table_gradient_binned(grad, inputs, offsets, B, L, S, H, gridtype, ctx.align_corners) if binned else torch.zeros_like(embeddings)
         if calc_grad_inputs:
             grad_inputs = (torch.empty_like if ctx.recompute else torch.zeros_like)(inputs, dtype=embeddings.dtype)

@@ -192,13 +192,19 @@ class _field_train_f32(Function):
             grad_emb = None
             if need_table:
                 inputs = ((x + field.bound) / (2 * field.bound)).contiguous()          # GridEncoder.forward (gridencoder/grid.py:144)
-                grad_emb = torch.zeros_like(embeddings)
-                dummy = torch.empty(1, dtype=torch.float32, device=x.device)
-                with _hip.timed("grid_encode_backward"):
-                    _hip.check(L.ngp_grid_encode_backward(_hip.ptr(grad_enc), _hip.ptr(inputs), _hip.ptr(embeddings), _hip.ptr(enc.offsets), _hip.ptr(grad_emb),
-                                                          M, 3, enc.level_dim, enc.num_levels, float(np.log2(enc.per_level_scale)), enc.base_resolution, 0,
-                                                          _hip.ptr(dummy), _hip.ptr(dummy), enc.gridtype_id, int(enc.align_corners), _hip.F32, _hip.stream()),
-                               "grid_encode_backward")
+                from gridencoder import grid as G
+                if (field.reproducible or G.BINNED_SCATTER_F32) and G.binned_f32_applies(3, enc.level_dim, embeddings, enc.offsets):
+                    # summed on chip with integer adds: the same bits on every run, and no zero fill (gridencoder/grid.py)
+                    grad_emb = G.table_gradient_binned_f32(grad_enc, inputs, enc.offsets, M, enc.num_levels, np.log2(enc.per_level_scale),
+                                                           enc.base_resolution, enc.gridtype_id, enc.align_corners)
+                else:
+                    grad_emb = torch.zeros_like(embeddings)
+                    dummy = torch.empty(1, dtype=torch.float32, device=x.device)
+                    with _hip.timed("grid_encode_backward"):
+                        _hip.check(L.ngp_grid_encode_backward(_hip.ptr(grad_enc), _hip.ptr(inputs), _hip.ptr(embeddings), _hip.ptr(enc.offsets),
+                                                              _hip.ptr(grad_emb), M, 3, enc.level_dim, enc.num_levels, float(np.log2(enc.per_level_scale)),
+                                                              enc.base_resolution, 0, _hip.ptr(dummy), _hip.ptr(dummy), enc.gridtype_id,
+                                                              int(enc.align_corners), _hip.F32, _hip.stream()), "grid_encode_backward")
         g_ws = [None] * 5
         if need_weights:
             at = 0
@@ -455,9 +461,12 @@ class NGPField(_ParamEpoch, nn.Module):
     """nerf/network.py: the same field with nn.Linear(bias=False) layers (32->64->16 ; 31->64->64->3)."""
 
     def __init__(self, bound=1, num_layers=2, hidden_dim=64, geo_feat_dim=15, num_layers_color=3, hidden_dim_color=64,
-                 density_scale=1, bg_radius=-1, num_layers_bg=2, hidden_dim_bg=64, fused_training=False):
+                 density_scale=1, bg_radius=-1, num_layers_bg=2, hidden_dim_bg=64, fused_training=False, reproducible=False):
         super().__init__()
         self.bound = bound
+        # the fused backward sums the table gradient on chip with integer adds (ngp_grid_scatter_binned_f32) instead of float atomics, whatever
+        # gridencoder.grid.BINNED_SCATTER_F32 says: with it the whole training step gives the same bits on every run
+        self.reproducible = bool(reproducible)
         self.density_scale = density_scale
         self.num_layers, self.num_layers_color, self.geo_feat_dim = num_layers, num_layers_color, geo_feat_dim
         self.encoder, self.in_dim = get_encoder("hashgrid", desired_resolution=2048 * bound)

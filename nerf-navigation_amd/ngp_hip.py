@@ -69,6 +69,8 @@ _SIGNATURES = {
     "ngp_grid_scatter_binned_listed": (c_int, [c_vp, c_vp, c_vp, c_vp, c_u32, c_u32, c_f32, c_u32, c_u32, c_u32, c_int, c_int, c_f32, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "ngp_grid_scatter_binned_phase_listed": (c_int, [c_int, c_vp, c_vp, c_vp, c_vp, c_u32, c_u32, c_u32, c_u32, c_f32, c_u32, c_u32, c_u32, c_int, c_int, c_f32, c_vp, c_vp,
                                                      c_vp, c_sz, c_vp]),
+    "ngp_grid_scatter_binned_f32_workspace": (c_sz, [c_u32, c_u32]),
+    "ngp_grid_scatter_binned_f32": (c_int, [c_vp, c_vp, c_vp, c_vp, c_u32, c_u32, c_f32, c_u32, c_u32, c_u32, c_int, c_f32, c_vp, c_sz, c_vp]),
     "ngp_adam_step": (c_int, [c_vp, c_u32, c_vp, c_vp, c_vp]),
     "ngp_train_mix_forward": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_u32, c_f32, c_u32, c_vp, c_vp, c_vp]),
     "ngp_train_mix_backward": (c_int, [c_vp, c_vp, c_u32, c_f32, c_u32, c_vp, c_vp]),

@@ -1,10 +1,11 @@
 """Time a training step of the DEFAULT float32 field (ngp.field.NGPField) through NGPTrainer(fp16=False): the op-by-op autograd chain against the
-native forward / backward of csrc/nav_train.hip (`fused_training=True`).  bench.py's training workload (ngp.workload's scene, teacher-rendered
+native forward / backward of csrc/nav_train.hip (`fused_training=True`), and against the same with the table gradient from the float32 binned scatter
+(`reproducible=True`: route `fused_reproducible`).  bench.py's training workload (ngp.workload's scene, teacher-rendered
 200 x 200 views, 4,096 rays per step, the seed fixed), in two phases: the first steps on the initial, nearly full occupancy grid, and after
 `--settle` further steps, when the grid has converged to the scene.  Every step is timed with its own pair of events; printed are the median, the
-quartiles and the extremes of `--steps` steps after `--warmup` untimed ones, and the points per step.  The two routes run in ONE process, phase by
+quartiles and the extremes of `--steps` steps after `--warmup` untimed ones, and the points per step.  The routes run in ONE process, phase by
 phase in alternation, so that clocks and neighbours are shared.
-   python tools/time_default_train.py [--steps 30] [--warmup 5] [--settle 1460] [--routes op_chain,fused]"""
+   python tools/time_default_train.py [--steps 30] [--warmup 5] [--settle 1460] [--routes op_chain,fused,fused_reproducible]"""
 import argparse
 import importlib
 import json
@@ -27,7 +28,7 @@ ap.add_argument("--steps", type=int, default=30)
 ap.add_argument("--warmup", type=int, default=5)
 ap.add_argument("--settle", type=int, default=1460)
 ap.add_argument("--rays", type=int, default=4096)
-ap.add_argument("--routes", default="op_chain,fused")
+ap.add_argument("--routes", default="op_chain,fused,fused_reproducible")
 args = ap.parse_args()
 dev = torch.device("cuda:0")
 res = 200
@@ -42,9 +43,10 @@ for view in range(8):
 
 
 class Route:
-    def __init__(self, fused):
-        torch.manual_seed(0)                                              # the same initial parameters for both routes
-        self.ren = NGPRenderer(NGPField(bound=W.BOUND, fused_training=fused).to(dev), bound=W.BOUND, cuda_ray=True, density_thresh=10.0).to(dev)
+    def __init__(self, name):
+        torch.manual_seed(0)                                              # the same initial parameters for every route
+        field = NGPField(bound=W.BOUND, fused_training=name != "op_chain", reproducible=name == "fused_reproducible")
+        self.ren = NGPRenderer(field.to(dev), bound=W.BOUND, cuda_ray=True, density_thresh=10.0).to(dev)
         self.tr = NGPTrainer(self.ren, lr=1e-2, iters=30000, fp16=False, steps_per_epoch=len(pool))
         self.gen = torch.Generator(device=dev).manual_seed(1)
         self.k = 0
@@ -73,7 +75,7 @@ class Route:
                     points_per_step=self.points(), loss=float(loss))
 
 
-routes = {name: Route(name == "fused") for name in args.routes.split(",")}
+routes = {name: Route(name) for name in args.routes.split(",")}
 for phase, untimed in (("initial grid", args.warmup), (f"after {args.settle} more steps", args.settle)):
     for name, r in routes.items():
         for _ in range(untimed):
