@@ -763,6 +763,46 @@ int ngp_filter_hessian(const ngp_nav_field_t* field_host, const void* prepared, 
                        const float* target, const int32_t* batch, float* hessian, float* grad, float* loss, float* dLdP,
                        void* workspace, size_t workspace_bytes, void* stream);
 
+/* The front of the time step: the sensor image's interest regions and the loop's batches (Estimator.find_POI, the dilation, coords[mask] and the draw,
+ * nav/estimator_helpers.py:181-204, 229-230; csrc/nav_features.hip, csrc/ngp_features.h, DESIGN.md §3.5 "Native interest regions").
+ *
+ * The detector is Lowe's difference-of-Gaussians detector with OpenCV's default parameters on an ALIGNED 2x upsample of the gray image, positions only
+ * (no orientations, no descriptors); DESIGN states every operation and its order, float32 with one rounding per operation.  It is not OpenCV's SIFT bit
+ * for bit and does not try to be.  Every entry point has a host twin (*_host, all pointers host memory, the same workspace layout) that runs the same
+ * functions pixel after pixel; device and host results are bit-identical, and two runs are.  No atomics.  Nothing here synchronises. */
+typedef struct {
+    float contrast;     /* 0.04: a keypoint's interpolated |D| * layers must reach it */
+    float edge;         /* 10:   bound on the principal curvature ratio */
+    float sigma;        /* 1.6:  blur of an octave's first level; 1 < sigma <= 4 */
+    uint32_t layers;    /* 3:    layers per octave (1..3); an octave has layers + 3 Gaussian levels */
+    uint32_t border;    /* 5:    candidates keep this distance from every edge of their octave (1..64) */
+} ngp_features_cfg_t;
+void ngp_features_default_cfg(ngp_features_cfg_t* cfg_host);
+/* bytes of the workspace of the three calls below, one layout: the pyramid (octave o: 6 float32 levels of [h_o,w_o], h_0 = 2H, h_{o+1} = ceil(h_o / 2),
+ * round(log2(min(2H, 2W))) - 2 octaves), the dilated mask [H,W] u8, per-chunk counts and a bitmap.  0 for H or W outside 16..4096. */
+size_t ngp_features_workspace(uint32_t H, uint32_t W);
+/* where the pieces lie, for tests and tools: out_host [40] = {octaves, byte offsets of the dilated mask, the counts and the bitmap, then per octave
+ * (12 slots, unused ones 0) h, w and the byte offset of its level 0}; levels follow each other h * w floats apart. */
+int ngp_features_layout(uint32_t H, uint32_t W, uint64_t* out_host);
+/* image [H,W,3] f32 in [0,1] -> mask [H,W] u8, 1 at int(y), int(x) of every keypoint, cleared on `stream` first.  6 * octaves + 1 launches.
+ * NGP_EINVAL: null pointers, a shape outside 16..4096, cfg fields outside the ranges above; NGP_EWORKSPACE: a null or short workspace. */
+int ngp_features_detect(const float* image, uint32_t H, uint32_t W, const ngp_features_cfg_t* cfg_host, uint8_t* mask, void* workspace,
+                        size_t workspace_bytes, void* stream);
+/* cv2.dilate(mask, ones(kernel_size, kernel_size), iterations = dil_iter), which is one square of side dil_iter * (kernel_size - 1) + 1 clipped at the
+ * image's edge, and the list of its pixels: regions [H*W,2] i32 (row, col), the first M written, in ascending column, then row (numpy's
+ * argwhere(mask.T)[:, ::-1]); count_dev [1] u32 = M.  A memset and three launches.  NGP_EINVAL: an even or zero kernel_size, dil_iter = 0, as above otherwise. */
+int ngp_features_regions(const uint8_t* mask, uint32_t H, uint32_t W, uint32_t kernel_size, uint32_t dil_iter, int32_t* regions, uint32_t* count_dev,
+                         void* workspace, size_t workspace_bytes, void* stream);
+/* batches [n_iter,B,2] i32: batches[k][j] = regions[p(j)], p a bijection of [0, M) keyed by (seed, k): distinct pixels within a batch by construction.
+ * M is the host's copy of the count.  One launch.  NGP_EINVAL: null pointers, B = 0, M = 0, M < B, M > 4096 * 4096 (more pixels than
+ * the largest image has: the permutation's halves are at most 12 bits wide), B * n_iter >= 2^31. */
+int ngp_features_draw(const int32_t* regions, uint32_t M, uint32_t B, uint32_t n_iter, uint32_t seed, int32_t* batches, void* stream);
+int ngp_features_detect_host(const float* image, uint32_t H, uint32_t W, const ngp_features_cfg_t* cfg_host, uint8_t* mask, void* workspace,
+                             size_t workspace_bytes);
+int ngp_features_regions_host(const uint8_t* mask, uint32_t H, uint32_t W, uint32_t kernel_size, uint32_t dil_iter, int32_t* regions, uint32_t* count_host,
+                              void* workspace, size_t workspace_bytes);
+int ngp_features_draw_host(const int32_t* regions, uint32_t M, uint32_t B, uint32_t n_iter, uint32_t seed, int32_t* batches);
+
 #ifdef __cplusplus
 }
 #endif

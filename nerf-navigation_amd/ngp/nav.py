@@ -816,8 +816,8 @@ class NativePoseFilter:
     """Estimator (nav/estimator_helpers.py) with its optimisation loop native: measurement_fn -> backward -> Adam run as ngp_filter_iterations, i.e. per
     iteration one launch for the batch's rays from the state, NativeNavQueries' run kernel forward, one launch for the loss, the run kernel backward
     and one launch for the chain back to the state, the Mahalanobis term and the Adam step.  `filter_cfg` takes the reference's keys batch_size,
-    lrate, N_iter, sig0, Q.  The feature detector and its dilation stay with the caller, who hands over `interest_regions`
-    ([M,2] (row, col) pairs) or ready batches; loss, state and gradient histories are device tensors.
+    lrate, N_iter, sig0, Q.  The caller hands over `interest_regions` ([M,2] (row, col) pairs) or ready batches, or lets the filter find them in the
+    sensor image (`features="native"`, below); loss, state and gradient histories are device tensors.
 
         filt = NativePoseFilter(filter_cfg, queries, start_state)          # queries: NativeNavQueries
         batches = filt.draw_batches(interest_regions, filt.iter, rng)
@@ -829,6 +829,13 @@ class NativePoseFilter:
 
         filt = NativePoseFilter(filter_cfg, queries, start_state, agent_cfg)
         xt = filt.estimate_state(target, action, interest_regions, rng=rng)  # filt.xt, filt.sig are the posterior
+
+    The front of the time step (find_POI, the dilation, coords[mask] and the draws: nav/estimator_helpers.py:181-204, 229-230) is native too
+    (csrc/nav_features.hip, DESIGN 3.5 "Native interest regions"): a difference-of-Gaussians detector with OpenCV's default parameters, the dilation by
+    filter_cfg's kernel_size / dil_iter (5 and 3 when absent), the ordered pixel list and a keyed draw without replacement, all on the current stream
+    with one 4-byte host read (the number of pixels M).
+
+        xt = filt.estimate_state(target, action, features="native", seed=7)   # the whole time step from the sensor image
     """
 
     def __init__(self, filter_cfg, queries, start_state=None, agent_cfg=None):
@@ -849,6 +856,7 @@ class NativePoseFilter:
         self.action = self.covariance_estimate = self.state_estimate = None
         self.iteration = 0
         self.hessian_grad = self.hessian_loss = self.hessian_dLdP = None
+        self._feat_ws = self._seed0 = None
 
     # -- plumbing ------------------------------------------------------------------------------------------------------
     def _vec(self, v):
@@ -965,6 +973,71 @@ class NativePoseFilter:
             out[k] = regions[rng.choice(M, size=B, replace=False)]
         return torch.from_numpy(out).to(self.device)
 
+    # -- the front of the time step, native ----------------------------------------------------------------------------------
+    def _features_workspace(self):
+        import ngp_hip as _hip
+        q = self.queries
+        nbytes = _hip.lib().ngp_features_workspace(int(q.H), int(q.W))
+        if nbytes == 0:
+            raise ValueError(f"the native detector takes images of 16 to 4096 pixels a side, not {q.H} x {q.W}")
+        if self._feat_ws is None or self._feat_ws.numel() < nbytes:
+            self._feat_ws = _hip.workspace(nbytes, self.device)
+        return self._feat_ws
+
+    def detect(self, target):
+        """the keypoint mask of the sensor image (ngp_features_detect with the default configuration): [H,W] uint8 on the device, 1 at int(y), int(x) of
+        every keypoint; no synchronisation"""
+        import ctypes
+        import ngp_hip as _hip
+        target = self._target(target)
+        q = self.queries
+        c = _hip.ngp_features_cfg_t()
+        _hip.lib().ngp_features_default_cfg(ctypes.byref(c))
+        ws = self._features_workspace()
+        mask = torch.empty(int(q.H), int(q.W), dtype=torch.uint8, device=self.device)
+        _hip.check(_hip.lib().ngp_features_detect(_hip.ptr(target), int(q.H), int(q.W), ctypes.byref(c), _hip.ptr(mask), _hip.ptr(ws), ws.numel(),
+                                                  _hip.stream()), "features_detect")
+        return mask
+
+    def interest_regions(self, target):
+        """find_POI and the dilation (nav/estimator_helpers.py:181-204): the pixels of the dilated keypoint mask as [M,2] int32 (row, col) pairs on the
+        device, in the order of the reference's coords[mask] (ascending column, then row).  Reads M back: the one host read of the front.  M = 0: an
+        empty tensor (the reference's "feature detection failed")."""
+        import ngp_hip as _hip
+        q = self.queries
+        mask = self.detect(target)
+        ws = self._features_workspace()
+        regions = torch.empty(int(q.H) * int(q.W), 2, dtype=torch.int32, device=self.device)
+        count = torch.empty(1, dtype=torch.int32, device=self.device)
+        _hip.check(_hip.lib().ngp_features_regions(_hip.ptr(mask), int(q.H), int(q.W), int(self.cfg.get("kernel_size", 5)), int(self.cfg.get("dil_iter", 3)),
+                                                   _hip.ptr(regions), _hip.ptr(count), _hip.ptr(ws), ws.numel(), _hip.stream()), "features_regions")
+        return regions[:int(count.item())]
+
+    def draw_batches_native(self, regions, n_iter, seed):
+        """the batches of n_iter iterations from `regions` ([M,2] int32 on the device, as interest_regions returns them) by ngp_features_draw: batch k is
+        regions[p_k(0 .. batch_size - 1)], p_k a bijection of [0, M) keyed by (seed, k) -> [n_iter, batch_size, 2] int32 on the device, no
+        synchronisation.  A draw of its own: it does not reproduce a numpy Generator's stream (draw_batches does)."""
+        import ngp_hip as _hip
+        if not (isinstance(regions, torch.Tensor) and regions.is_cuda and regions.dtype == torch.int32 and regions.dim() == 2 and regions.shape[1] == 2):
+            raise ValueError("draw_batches_native takes regions as interest_regions returns them: [M, 2] int32 on the GPU")
+        M, B = int(regions.shape[0]), self.batch_size
+        if M < B:
+            raise ValueError(f"{M} interest points cannot fill a batch of {B} without replacement")
+        regions = regions.contiguous()
+        out = torch.empty(int(n_iter), B, 2, dtype=torch.int32, device=self.device)
+        _hip.check(_hip.lib().ngp_features_draw(_hip.ptr(regions), M, B, int(n_iter), int(seed) & 0xFFFFFFFF, _hip.ptr(out), _hip.stream()), "features_draw")
+        return out
+
+    def step_seed(self, seed=None):
+        """the draw's seed in time step `iteration`: (seed + 0x9E3779B9 * iteration) mod 2^32.  seed = None: 32 bits from the operating system, taken
+        once per filter and kept, so that later time steps follow from it by the same rule."""
+        if seed is None:
+            if self._seed0 is None:
+                import os
+                self._seed0 = int.from_bytes(os.urandom(4), "little")
+            seed = self._seed0
+        return (int(seed) + 0x9E3779B9 * int(self.iteration)) & 0xFFFFFFFF
+
     def cost_and_gradient(self, state, start_state, sig, target, batch):
         """measurement_fn(state, start_state, sig, target, batch) and its gradient: dict(loss, rgb_loss, grad [12]), device tensors"""
         batches = self._batches(batch)
@@ -976,11 +1049,12 @@ class NativePoseFilter:
         process = delta @ self.sig_inv.double() @ delta
         return dict(loss=loss[0], rgb_loss=loss[0] - process.to(self.device, torch.float32), grad=adam[24:36])
 
-    def estimate_relative_pose(self, target, start_state, sig, batches):
+    def estimate_relative_pose(self, target, start_state, sig, batches, check=True):
         """Estimator.estimate_relative_pose's loop (nav/estimator_helpers.py:207-291): N_iter Adam iterations from start_state + 1e-6 with fresh
-        moments, all queued in one call.  Keeps losses [N_iter], states and grads [N_iter,12] (before each step), target and the last batch."""
+        moments, all queued in one call.  Keeps losses [N_iter], states and grads [N_iter,12] (before each step), target and the last batch.
+        check=False skips the range check of the batches (a host read): for batches the library itself drew from pixels of the image."""
         n = self.iter
-        batches = self._batches(batches)
+        batches = self._batches(batches, check)
         if batches.shape[0] < n:
             raise ValueError(f"{n} iterations need {n} batches, got {batches.shape[0]}")
         target = self._target(target)
@@ -1068,17 +1142,27 @@ class NativePoseFilter:
                                                    _hip.ptr(out["A"]), _hip.ptr(out["sig_prop"]), _hip.stream()), "filter_propagate")
         return out
 
-    def estimate_state(self, target, action, interest_regions=None, batches=None, rng=None):
+    def estimate_state(self, target, action, interest_regions=None, batches=None, rng=None, features=None, seed=None):
         """Estimator.estimate_state (nav/estimator_helpers.py:347-406): propagate the estimate and its covariance through the dynamics, run the loop from
         there, take the Hessian at the result and make its nearest positive-definite matrix's inverse the new covariance.  target: the sensor image,
         float32 [H,W,3] on the GPU; the loop's batches are drawn from `interest_regions` ([M,2] (row, col) pairs, with `rng`, a numpy Generator) unless
         `batches` [N_iter,B,2] are given.  Empty interest_regions and no batches: the reference's "feature detection failed" path (:185-190, :381) -- the
         propagated state is returned, no loop and no Hessian run, and `sig` stays the previous posterior.  Keeps xt, sig, action, covariance_estimate,
         state_estimate, iteration.  One difference from the reference: A is the Jacobian at the previous estimate (the point the dynamics are evaluated
-        at, one launch), where :362 evaluates it at the propagated one."""
+        at, one launch), where :362 evaluates it at the propagated one.
+        features="native": the regions come from `target` itself (interest_regions) and the batches from draw_batches_native with step_seed(seed); no
+        pixel of the front is computed on the host.  No keypoint at all is the "feature detection failed" path."""
         import numpy as np
         if self.xt is None:
             raise ValueError("estimate_state needs the estimate of the previous time step: NativePoseFilter(filter_cfg, queries, start_state, agent_cfg)")
+        if features is not None:
+            if features != "native":
+                raise ValueError(f"features must be None or 'native', got {features!r}")
+            if interest_regions is not None or batches is not None or rng is not None:
+                raise ValueError("features='native' finds the regions and draws the batches itself: pass none of interest_regions, batches, rng")
+            regions = self.interest_regions(target)
+            if regions.shape[0]:
+                batches = self.draw_batches_native(regions, self.iter, self.step_seed(seed))
         prop = self.propagate(self.xt, action, self.sig, self.Q)
         xt_prop, sig_prop = prop["state"], prop["sig_prop"]
         self.action = torch.as_tensor(action).detach().cpu().reshape(-1).tolist()
@@ -1090,7 +1174,7 @@ class NativePoseFilter:
             self.losses, self.states = [], []
             xt = xt_prop.clone()
         else:
-            xt = self.estimate_relative_pose(target, xt_prop, sig_prop, batches)
+            xt = self.estimate_relative_pose(target, xt_prop, sig_prop, batches, check=features is None)
             hess = self.measurement_hessian(xt, xt_prop, sig_prop, native=True)
             self.sig = self.covariance(hess).float().to(self.device)
         self.xt = xt

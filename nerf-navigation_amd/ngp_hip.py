@@ -148,6 +148,15 @@ _SIGNATURES = {
     "ngp_filter_rays": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "ngp_filter_propagate": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "ngp_filter_hessian": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "ngp_features_default_cfg": (None, [c_vp]),
+    "ngp_features_workspace": (c_sz, [c_u32, c_u32]),
+    "ngp_features_layout": (c_int, [c_u32, c_u32, c_vp]),
+    "ngp_features_detect": (c_int, [c_vp, c_u32, c_u32, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "ngp_features_regions": (c_int, [c_vp, c_u32, c_u32, c_u32, c_u32, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "ngp_features_draw": (c_int, [c_vp, c_u32, c_u32, c_u32, c_u32, c_vp, c_vp]),
+    "ngp_features_detect_host": (c_int, [c_vp, c_u32, c_u32, c_vp, c_vp, c_vp, c_sz]),
+    "ngp_features_regions_host": (c_int, [c_vp, c_u32, c_u32, c_u32, c_u32, c_vp, c_vp, c_vp, c_sz]),
+    "ngp_features_draw_host": (c_int, [c_vp, c_u32, c_u32, c_u32, c_u32, c_vp]),
 }
 
 EXPORTS = tuple(_SIGNATURES)
@@ -203,6 +212,11 @@ class ngp_filter_cfg_t(ctypes.Structure):
 class ngp_filter_dyn_t(ctypes.Structure):
     """include/ngp_hip.h: ngp_filter_dyn_t"""
     _fields_ = [("dt", c_f32), ("mass", c_f32), ("g", c_f32), ("I", c_f32 * 9)]
+
+
+class ngp_features_cfg_t(ctypes.Structure):
+    """include/ngp_hip.h: ngp_features_cfg_t"""
+    _fields_ = [("contrast", c_f32), ("edge", c_f32), ("sigma", c_f32), ("layers", c_u32), ("border", c_u32)]
 
 
 FILTER_ADAM_FLOATS = 37                                      # include/ngp_hip.h: NGP_FILTER_ADAM_FLOATS
