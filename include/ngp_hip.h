@@ -803,6 +803,26 @@ int ngp_features_regions_host(const uint8_t* mask, uint32_t H, uint32_t W, uint3
                               void* workspace, size_t workspace_bytes);
 int ngp_features_draw_host(const int32_t* regions, uint32_t M, uint32_t B, uint32_t n_iter, uint32_t seed, int32_t* batches);
 
+/* ------------------------------------------------------------------------ */
+/* Agent and sensor of the navigation loop (reference: Agent.step, nav/agent_helpers.py:65-99, without its Blender subprocess; csrc/nav_agent.hip,
+ * DESIGN.md §3.5 "Native agent and the closed loop").  Each entry point: one launch on `stream`, no host read, no atomics, no workspace. */
+/* ------------------------------------------------------------------------ */
+
+/* One step of the true state: drone_dynamics (the functions behind ngp_filter_propagate, float64 from the float32 inputs) plus `noise`, added in float64
+ * and rounded once.  state [12], action [4], noise [12] or NULL (NULL is a zero noise vector), next_state [12]: device float32; next_state may be `state`.
+ * blender_pose [16] (may be NULL): row-major 4 x 4, rot_x(pi/2) R(next_state[6:9]) with translation next_state[:3], the matrix the reference writes for
+ * Blender; body_pose [16] (may be NULL): that matrix with rot_x(-pi/2) applied back, what Agent.step returns as true_pose.  Both follow from the
+ * unrounded float64 state, with rot_x's cosine the reference's float32 one.  Refusals as for ngp_filter_propagate. */
+int ngp_agent_step(const ngp_filter_dyn_t* dyn_host, const float* state, const float* action, const float* noise, float* next_state,
+                   float* blender_pose, float* body_pose, void* stream);
+/* The rays of every pixel of the sensor camera at `state` [12]: rays_o, rays_d [H*W,3], pixel (row, col) is ray row * W + col.  The pose chain and the
+ * ray arithmetic are those of ngp_filter_rays, bit for bit.  Reads H, W and intrinsics of cfg_host; H * W < 2^31. */
+int ngp_agent_rays(const ngp_filter_cfg_t* cfg_host, const float* state, float* rays_o, float* rays_d, void* stream);
+/* The camera's 8-bit round trip over image [N,3] f32: c = clamp(image, 0, 1) (a NaN reads as 0); png [N,3] u8 = (uint8)(c * 255.0f), a float32 product
+ * truncated; target [N,3] f32 = (float)((double)png / 255.0).  Any N (0 launches nothing); 16-byte stores when image and target are 16-byte and png
+ * 4-byte aligned, element by element otherwise. */
+int ngp_agent_sensor(const float* image, uint8_t* png, float* target, uint32_t N, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

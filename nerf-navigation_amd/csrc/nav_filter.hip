@@ -18,6 +18,7 @@
 #include "ngp_nav_step.h"
 #include "ngp_camera.h"
 #include "ngp_filter_step.h"
+#include "ngp_filter_pose.h"                                                 // NF_C90, nf_rodrigues, nf_rotation, nf_pose: shared with nav_agent.hip
 
 static constexpr uint32_t NF_THREADS = 256, NF_WAVES = NF_THREADS / 64;
 static constexpr uint32_t NF_MAX_B = 1u << 20, NF_MAX_T = 4096;             // num_steps: what ngp_nav_run_forward accepts
@@ -25,41 +26,11 @@ static constexpr uint32_t NF_SUMS = 13;                                      // 
 enum : uint32_t { NF_M = 0, NF_V = 12, NF_G = 24, NF_STEP = 36 };            // adam_state (NGP_FILTER_ADAM_FLOATS)
 static_assert(NGP_FILTER_ADAM_FLOATS == NF_STEP + 1, "adam_state layout");
 
-// rot_x(pi / 2) as the reference builds it: cos and sin of (float)(pi / 2) in float32
-#define NF_C90 (-4.37113883e-08f)
-
 struct nf_view { float fx, fy, cx, cy; uint32_t W, H; float aabb[6]; float min_near; };
 struct nf_step_args {
     float start[12], sig_inv[144];
     ngp_adam_coef adam;                                                      // zeroed where no step is taken (ngp_filter_hessian)
 };
-
-// vec_to_rot_matrix (nav/math_utils.py:159-174) and what its backward needs
-struct nf_rodrigues { float K[9], M[9], R[9], a, d, sn, cs; };
-
-__device__ __forceinline__ void nf_rotation(const float* r, nf_rodrigues& Q) {
-    Q.a = sqrtf((r[0] * r[0] + r[1] * r[1]) + r[2] * r[2]);
-    Q.d = 1e-10f + Q.a;
-    const float k0 = r[0] / Q.d, k1 = r[1] / Q.d, k2 = r[2] / Q.d;
-    const float K[9] = {0.f, -k2, k1, k2, 0.f, -k0, -k1, k0, 0.f};
-    Q.sn = sinf(Q.a); Q.cs = cosf(Q.a);
-    const float omc = 1.0f - Q.cs;
-#pragma unroll
-    for (int e = 0; e < 9; e++) { Q.K[e] = K[e]; Q.M[e] = omc * K[e]; }
-    float MK[9];
-    nfs_matmul3(Q.M, Q.K, MK);
-#pragma unroll
-    for (int e = 0; e < 9; e++) Q.R[e] = ((e % 4 == 0 ? 1.0f : 0.0f) + Q.sn * K[e]) + MK[e];
-}
-
-// measurement_fn's pose (nav/estimator_helpers.py:301-309): P = cycle (rot_x(pi/2) R) diag(1, -1, -1), T = cycle position (nerf_matrix_to_ngp_torch)
-__device__ __forceinline__ void nf_pose(const float* state, nf_rodrigues& Q, float* P, float* T) {
-    const float r[3] = {state[6], state[7], state[8]};
-    nf_rotation(r, Q);
-    nfs_camera_axes(Q.R, (double)NF_C90, P);
-#pragma unroll
-    for (int i = 0; i < 3; i++) T[i] = state[(i + 1) % 3];
-}
 
 // the backward of nf_pose's rotation part: GP = dL/dP -> dL/d state[6:9]
 __device__ __forceinline__ void nf_pose_backward(const float* r, const nf_rodrigues& Q, const float* GP, float* gr) {

@@ -295,7 +295,7 @@ class _nav_run(torch.autograd.Function):
         ren = owner.renderer
         aabb_t = ren._aabb()
         nears, fars = raymarching.near_far_from_aabb(rays_o, rays_d, aabb_t, ren.min_near)
-        aabb = (ctypes.c_float * 6)(*[float(v) for v in aabb_t.tolist()])
+        aabb = (ctypes.c_float * 6)(*ren._aabb_host())
         bgc = (ctypes.c_float * 3)(*bg)
         image = torch.empty(N, 3, dtype=torch.float32, device=rays_o.device)
         depth = torch.empty(N, dtype=torch.float32, device=rays_o.device)
@@ -1198,3 +1198,232 @@ class NativePoseFilter:
         import numpy as np
         h = hessian.detach().cpu().numpy() if isinstance(hessian, torch.Tensor) else np.asarray(hessian)
         return torch.inverse(torch.from_numpy(nearest_pd(h)))
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# the agent and its sensor on the device (csrc/nav_agent.hip), and the loop that closes over planner, agent and filter
+# ------------------------------------------------------------------------------------------------------------------------
+def _vec_to_rot_matrix(rot_vec):
+    """vec_to_rot_matrix (nav/math_utils.py:159-174) in torch, in the dtype and on the device of `rot_vec` [3]"""
+    kw = dict(dtype=rot_vec.dtype, device=rot_vec.device)
+    angle = torch.norm(rot_vec, dim=-1, keepdim=True)
+    S = _hat(rot_vec / (1e-10 + angle))
+    return torch.eye(3, **kw) + torch.sin(angle) * S + (1 - torch.cos(angle)) * S @ S
+
+
+def _rot_matrix_to_vec(R):
+    """rot_matrix_to_vec (nav/math_utils.py:116-157) in torch for one [3,3] matrix, with acos_safe's straight line beyond |x| = 1 - 1e-7 and the zero vector
+    at angle 0.  Reads the angle on the host (two branches): for the loop's set-up, not its steps."""
+    import numpy as np
+    eps = 1e-7
+    x = (torch.diagonal(R).sum(-1) - 1) / 2
+    if abs(x) <= 1 - eps:
+        angle = torch.acos(x)
+    else:
+        sign = torch.sign(x)
+        angle = torch.acos(sign * (1 - eps)) - (np.arccos(1 - eps) / eps) * sign * (abs(x) - 1 + eps)
+    if angle == 0:
+        return torch.zeros(3, dtype=R.dtype, device=R.device)
+    return angle / (2 * torch.sin(angle + 1e-10)) * torch.stack([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
+
+
+def _rot_x(phi, **kw):
+    """rot_x (nav/math_utils.py:17-20): cos and sin of the float32 angle"""
+    phi = torch.tensor(phi, dtype=torch.float32)
+    c, s = float(torch.cos(phi)), float(torch.sin(phi))
+    return torch.tensor([[1., 0., 0.], [0., c, -s], [0., s, c]], **kw)
+
+
+def mpc_action_row(iteration, steps):
+    """The loop's action rule (simulate.py:73-76): before `steps - 5` the planner's next action (None: get_next_action(), row 0 of the plan that was just
+    replanned); from there on row `iteration - steps + 5` of get_actions(), the tail of the last plan, which is no longer replanned."""
+    return None if iteration < steps - 5 else iteration - steps + 5
+
+
+class NativeAgent:
+    """Agent (nav/agent_helpers.py) with the world seen through a renderer instead of a Blender subprocess.  A `step` is four queued operations and no host
+    synchronisation: ngp_agent_step (the dynamics the filter propagates with, plus noise, and the two poses), ngp_agent_rays (the sensor camera's rays at the
+    new state, by the filter's own pose chain), the render, ngp_agent_sensor (the camera's 8-bit round trip).
+
+        agent = NativeAgent(agent_cfg, queries)                  # agent_cfg: the reference's keys x0, dt, mass, g, I; queries: NativeNavQueries
+        true_pose, true_state, img = agent.step(action, noise)   # [4,4] f32, [12] f32, [H,W,3] u8 on the device; agent.target: [H,W,3] f32 for estimate_state
+
+    sensor: the renderer the world is seen through; it may wrap another field than the map `queries` holds.  A renderer with cuda_ray=True and a built
+    occupancy bitfield is rendered with render_fused over the rays (the one-launch frame, bg_color = 1); sensor=None (or queries' own renderer) renders with
+    queries.render_fn in max_ray_batch chunks under no_grad: exactly the image the filter predicts.  What differs from the reference's sensor: the field
+    renders at the sensor's resolution onto white (no half-resolution resize, no RGBA), and values are clamped to [0, 1] before the 8-bit round trip.
+    `states_history` [iter + 1, 12] stays on the device; save_data is its one host read."""
+
+    def __init__(self, agent_cfg, queries, sensor=None):
+        import ngp_hip as _hip
+        if not isinstance(queries, NativeNavQueries):
+            raise ValueError(f"NativeAgent needs a NativeNavQueries (the fused float32 queries), got {type(queries).__name__}")
+        self.queries = queries
+        self.device = queries.native.field.encoder.embeddings.device
+        self.cfg = agent_cfg
+        self.dt, self.g, self.mass, self.I = agent_cfg["dt"], agent_cfg["g"], agent_cfg["mass"], agent_cfg["I"]
+        d = _hip.ngp_filter_dyn_t()
+        d.dt, d.mass, d.g = float(self.dt), float(self.mass), float(self.g)
+        d.I[:] = [float(v) for v in torch.as_tensor(self.I).detach().cpu().reshape(-1).tolist()]
+        self._dyn = d
+        v = _hip.ngp_filter_cfg_t()                          # the view part: what ngp_agent_rays reads
+        v.H, v.W = int(queries.H), int(queries.W)
+        v.intrinsics[:] = [float(x) for x in queries.intrinsics]
+        self._view = v
+        self.H, self.W = int(queries.H), int(queries.W)
+        self.sensor = sensor
+        self._frame = False
+        if sensor is not None and getattr(sensor, "cuda_ray", False):
+            sensor._default_frame_field("NativeAgent")       # a ValueError that names what the one-launch frame does not render
+            if not bool(sensor.density_bitfield.any()):
+                raise ValueError("NativeAgent: the sensor's occupancy bitfield is empty: build it first (update_extra_state or load_density_grid)")
+            if sensor.density_bitfield.device != self.device:
+                raise ValueError(f"NativeAgent: the sensor lives on {sensor.density_bitfield.device}, the queries on {self.device}")
+            self._frame = True
+        elif sensor is not None and sensor is not queries.renderer:
+            raise ValueError("NativeAgent: a sensor with cuda_ray=False is rendered through queries.render_fn, so it must be the queries' own renderer; "
+                             "a sensor over another field needs cuda_ray=True and a built bitfield")
+        self.iter = 0
+        self._hist = torch.empty(64, 12, dtype=torch.float32, device=self.device)
+        self._hist[0] = torch.as_tensor(agent_cfg["x0"]).detach().to(self.device, torch.float32).reshape(12)
+        self._n = 1
+        self.x = self._hist[0]
+        self.target = self.img = None
+        self.pose = None                                     # the matrix the reference writes for Blender, [4,4] on the device
+
+    @property
+    def states_history(self):
+        return self._hist[:self._n]
+
+    def _next_row(self):
+        if self._n == self._hist.shape[0]:
+            self._hist = torch.cat([self._hist, torch.empty_like(self._hist)])
+        row = self._hist[self._n]
+        self._n += 1
+        return row
+
+    def rays(self, state):
+        """the sensor camera's rays at `state` (ngp_agent_rays): rays_o, rays_d [H*W,3], pixel (row, col) is ray row * W + col"""
+        import ctypes
+        import ngp_hip as _hip
+        N = self.H * self.W
+        rays_o = torch.empty(N, 3, dtype=torch.float32, device=self.device)
+        rays_d = torch.empty(N, 3, dtype=torch.float32, device=self.device)
+        _hip.check(_hip.lib().ngp_agent_rays(ctypes.byref(self._view), _hip.ptr(state), _hip.ptr(rays_o), _hip.ptr(rays_d), _hip.stream()), "agent_rays")
+        return rays_o, rays_d
+
+    def render(self, rays_o, rays_d):
+        """the observation before the camera: [H*W,3] float32"""
+        if self._frame:
+            return self.sensor.render_fused(rays_o, rays_d, image_width=self.W, bg_color=1)["image"]
+        with torch.no_grad():
+            return self.queries.render_fn(rays_o[None], rays_d[None])["image"].reshape(-1, 3)
+
+    def sense(self, image):
+        """ngp_agent_sensor: image [N,3] float32 -> (png uint8, target float32), both [H,W,3]"""
+        import ngp_hip as _hip
+        image = image.contiguous()
+        png = torch.empty(self.H, self.W, 3, dtype=torch.uint8, device=self.device)
+        target = torch.empty(self.H, self.W, 3, dtype=torch.float32, device=self.device)
+        _hip.check(_hip.lib().ngp_agent_sensor(_hip.ptr(image), _hip.ptr(png), _hip.ptr(target), self.H * self.W, _hip.stream()), "agent_sensor")
+        return png, target
+
+    def _observe(self, state):
+        rays_o, rays_d = self.rays(state)
+        self.img, self.target = self.sense(self.render(rays_o, rays_d))
+        return self.img
+
+    def step(self, action, noise=None):
+        """Agent.step (nav/agent_helpers.py:65-99): -> (true_pose [4,4], true_state [12], img uint8 [H,W,3]), device tensors; keeps x, iter, target, pose"""
+        import ctypes
+        import ngp_hip as _hip
+        action = torch.as_tensor(action).detach().to(self.device, torch.float32).reshape(4).contiguous()
+        if noise is not None:
+            noise = torch.as_tensor(noise).detach().to(self.device, torch.float32).reshape(12).contiguous()
+        new = self._next_row()
+        poses = torch.empty(2, 4, 4, dtype=torch.float32, device=self.device)
+        _hip.check(_hip.lib().ngp_agent_step(ctypes.byref(self._dyn), _hip.ptr(self.x), _hip.ptr(action), _hip.ptr(noise), _hip.ptr(new), _hip.ptr(poses[0]),
+                                             _hip.ptr(poses[1]), _hip.stream()), "agent_step")
+        self.x, self.pose = new, poses[0]
+        img = self._observe(new)
+        self.iter += 1
+        return poses[1], new, img
+
+    def state2image(self, state):
+        """Agent.state2image (nav/agent_helpers.py:101-122): the state is taken as it is (no dynamics) and observed -> (pose [4,4] as written for Blender,
+        state [12], img)"""
+        new = self._next_row()
+        new.copy_(torch.as_tensor(state).detach().to(self.device, torch.float32).reshape(12))
+        self.x = new
+        kw = dict(dtype=torch.float32, device=self.device)
+        pose = torch.eye(4, **kw)
+        pose[:3, :3] = _rot_x(torch.pi / 2, **kw) @ _vec_to_rot_matrix(new[6:9])
+        pose[:3, 3] = new[:3]
+        self.pose = pose
+        return pose, new, self._observe(new)
+
+    def save_data(self, filename):
+        """Agent.save_data: {"true_states": [iter + 1 rows of 12]}; the one place the history is read to the host"""
+        import json
+        with open(filename, "w+") as f:
+            json.dump({"true_states": self.states_history.cpu().tolist()}, f)
+
+
+SIMULATE_FOLDERS = ("init_poses", "init_costs", "replan_poses", "replan_costs", "estimator_data")
+
+
+def simulate(planner_cfg, agent_cfg, filter_cfg, extra_cfg, queries, sensor=None, basefolder=None, generator=None, interest_regions=None, seed=None):
+    """simulate.simulate (simulate.py:18-102) over the native planner, agent and filter: A* and learn_init, then per MPC step the planner's action, the agent's
+    noisy step and observation, the filter's time step and, before `steps - 5`, update_state and learn_update.
+
+    planner_cfg holds start_state and end_state (18-vectors) beside the planner's keys, and optionally "a_star": keyword arguments of a_star_init (side,
+    kernel_size, threshold, lo, hi, noise_std) for a map whose free space the reference's constants do not fit; extra_cfg holds mpc_noise_mean and mpc_noise_std ([12] tensors, on the
+    device `generator` belongs to).  generator: torch.normal's, for the process noise.  The filter finds its regions in the observation
+    (features="native", the draw keyed by `seed`) unless interest_regions ([M,2] (row, col)) are given, which are then used every step with
+    numpy's default_rng(seed).  seed also seeds a_star_init's path noise; None leaves all three to the global / operating-system sources, as the reference.
+    basefolder: a directory (created when missing) that receives the reference's five sub-folders, init_* and replan_* from the planner, estimator_data/
+    step{n}.json from the filter and true_states.json from the agent; None: nothing touches the disk.  Never prompts.
+    -> dict(true_states [steps+1,12], estimates [steps,12], actions [steps,4], noises [steps,12] on the device; planner, agent, filter)."""
+    import pathlib
+    import numpy as np
+    start_state, end_state = planner_cfg["start_state"], planner_cfg["end_state"]
+    if basefolder is not None:
+        basefolder = pathlib.Path(basefolder)
+        basefolder.mkdir(parents=True, exist_ok=True)
+        for name in SIMULATE_FOLDERS:
+            (basefolder / name).mkdir(exist_ok=True)
+    traj = NativePlanner(start_state, end_state, planner_cfg, queries)
+    if basefolder is not None:
+        traj.basefolder = basefolder
+    traj.a_star_init(generator=None if seed is None else torch.Generator().manual_seed(int(seed)), **planner_cfg.get("a_star", {}))
+    traj.learn_init()
+    # 18-vector (rotation matrix) -> 12-vector (rotation vector)
+    s18 = torch.as_tensor(start_state).detach().cpu().float()
+    start12 = torch.cat([s18[:6], _rot_matrix_to_vec(s18[6:15].reshape(3, 3)), s18[15:]], dim=-1).to(traj.device)
+    agent_cfg = dict(agent_cfg, x0=start12)
+    agent = NativeAgent(agent_cfg, queries, sensor)
+    filt = NativePoseFilter(filter_cfg, queries, start12, agent_cfg)
+    steps = int(traj.get_actions().shape[0])
+    noise_mean, noise_std = extra_cfg["mpc_noise_mean"], extra_cfg["mpc_noise_std"]
+    rng = None if interest_regions is None else np.random.default_rng(seed)
+    kw = dict(dtype=torch.float32, device=traj.device)
+    estimates, actions, noises = torch.empty(steps, 12, **kw), torch.empty(steps, 4, **kw), torch.empty(steps, 12, **kw)
+    for it in range(steps):
+        row = mpc_action_row(it, steps)
+        action = traj.get_next_action().clone().detach() if row is None else traj.get_actions()[row, :]
+        noise = torch.normal(noise_mean, noise_std, generator=generator)
+        agent.step(action, noise=noise)
+        if interest_regions is None:
+            state_est = filt.estimate_state(agent.target, action, features="native", seed=seed)
+        else:
+            state_est = filt.estimate_state(agent.target, action, interest_regions, rng=rng)
+        if basefolder is not None:
+            filt.save_data(basefolder / "estimator_data" / f"step{filt.iteration - 1}.json")
+        estimates[it], actions[it], noises[it] = state_est, action, noise.to(**kw)
+        if row is None:
+            # 12-vector -> 18-vector; the planner replans from the estimate
+            traj.update_state(torch.cat([state_est[:6], _vec_to_rot_matrix(state_est[6:9]).reshape(-1), state_est[9:]], dim=-1))
+            traj.learn_update(it)
+    if basefolder is not None:
+        agent.save_data(basefolder / "true_states.json")
+    return dict(true_states=agent.states_history.clone(), estimates=estimates, actions=actions, noises=noises, planner=traj, agent=agent, filter=filt)

@@ -151,6 +151,17 @@ class NGPRenderer(nn.Module):
     def _aabb(self):
         return self.aabb_train if self.training else self.aabb_infer
 
+    def _aabb_host(self):
+        """_aabb() as six host floats.  The buffer is read back only when its storage or version changed, so a caller that hands the box to a
+        kernel as a host argument (the frame, the nav queries) does not synchronise per call."""
+        t = self._aabb()
+        key = (t.data_ptr(), t._version, str(t.device))
+        cached = self.__dict__.get("_aabb_host_cache")
+        if cached is None or cached[0] != key:
+            cached = (key, [float(v) for v in t.tolist()])
+            self.__dict__["_aabb_host_cache"] = cached
+        return cached[1]
+
     # ------------------------------------------------------------------------------------------------------------
     # occupancy-grid path, op by op
     # ------------------------------------------------------------------------------------------------------------
@@ -259,7 +270,7 @@ class NGPRenderer(nn.Module):
         if bg_color is None:
             bg_color = 1
         bg = (ctypes.c_float * 3)(*([float(bg_color)] * 3 if np.isscalar(bg_color) else [float(v) for v in bg_color]))
-        aabb = (ctypes.c_float * 6)(*[float(v) for v in self._aabb().tolist()])
+        aabb = (ctypes.c_float * 6)(*self._aabb_host())
         L = _hip.lib()
         ws = _hip.workspace(L.ngp_nav_render_frame_workspace(N), device)
         with torch.cuda.device(device):

@@ -157,6 +157,9 @@ _SIGNATURES = {
     "ngp_features_detect_host": (c_int, [c_vp, c_u32, c_u32, c_vp, c_vp, c_vp, c_sz]),
     "ngp_features_regions_host": (c_int, [c_vp, c_u32, c_u32, c_u32, c_u32, c_vp, c_vp, c_vp, c_sz]),
     "ngp_features_draw_host": (c_int, [c_vp, c_u32, c_u32, c_u32, c_u32, c_vp]),
+    "ngp_agent_step": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "ngp_agent_rays": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "ngp_agent_sensor": (c_int, [c_vp, c_vp, c_vp, c_u32, c_vp]),
 }
 
 EXPORTS = tuple(_SIGNATURES)
