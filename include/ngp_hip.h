@@ -742,6 +742,30 @@ int ngp_filter_iterations(const ngp_nav_field_t* field_host, const void* prepare
 int ngp_filter_rays(const ngp_filter_cfg_t* cfg_host, const float* state, const int32_t* batch, float* rays_o, float* rays_d, float* nears,
                     float* fars, void* stream);
 
+/* Multi-start (DESIGN.md §3.5 "Multi-start pose filter"): K hypotheses minimise ONE objective -- one cfg_host (start_state, the Mahalanobis centre;
+ * sig_inv; Adam's constants), one target, one set of batches -- from K initial points, as one sequence of five launches per iteration whatever K is:
+ * hypothesis k owns rays [k B, (k + 1) B) of a K B-ray run.  Row k of every output is bit for bit what ngp_filter_iterations gives from states[k]. */
+#define NGP_FILTER_MULTI_MAX_K 64u
+/* bytes of the workspace of ngp_filter_iterations_multi: the pieces of ngp_filter_workspace for K B rays, with K slices of loss partials; at K = 1 the
+ * same size.  0 outside 1 <= K <= 64, K B <= 2^20, and the B, num_steps of ngp_filter_workspace. */
+size_t ngp_filter_multi_workspace(uint32_t K, uint32_t B, uint32_t num_steps);
+/* n_iter iterations of K hypotheses: 5 launches per iteration on `stream`, no synchronisation, no host read.  states [K,12] are updated in place,
+ * adam_states [K,NGP_FILTER_ADAM_FLOATS] likewise; target, batches, first_iter, update as for ngp_filter_iterations (the batches are shared: every
+ * hypothesis renders the same pixels).  losses [n_iter,K], states_out [n_iter,K,12], grads_out [n_iter,K,12] (each may be NULL): the values BEFORE each step.
+ * The mean of the loss is over one hypothesis' B rays.  Refused on the host before anything is queued: K = 0, K > 64, K B > 2^20, whatever
+ * ngp_filter_iterations refuses, and (NGP_EWORKSPACE) a null workspace or one shorter than ngp_filter_multi_workspace(K, B, num_steps). */
+int ngp_filter_iterations_multi(const ngp_nav_field_t* field_host, const void* prepared, const ngp_filter_cfg_t* cfg_host, uint32_t K,
+                                float* states, float* adam_states, const float* target, const int32_t* batches, uint32_t first_iter,
+                                uint32_t n_iter, int update, float* losses, float* states_out, float* grads_out, void* workspace,
+                                size_t workspace_bytes, void* stream);
+/* The hypothesis with the best loss: ONE launch of one wave, no host read.  losses [K], states [K,12] -> best_state [12], best_loss [1], best_index [1].
+ * The rule: indices are scanned in ascending order from best = 0; candidate i replaces the best when losses[i] < losses[best], or when losses[best] is
+ * NaN and losses[i] is not.  So ties keep the lowest index, a NaN never beats a number, and K NaNs give index 0.  1 <= K <= 64, no null pointer. */
+int ngp_filter_select(const float* losses, const float* states, uint32_t K, float* best_state, float* best_loss, uint32_t* best_index,
+                      void* stream);
+/* The same function compiled for the host (all pointers host memory): the rule, testable without a device. */
+int ngp_filter_select_host(const float* losses, const float* states, uint32_t K, float* best_state, float* best_loss, uint32_t* best_index);
+
 /* The rest of the estimator's time step (Estimator.estimate_state, nav/estimator_helpers.py:347-406; DESIGN.md §3.5 "Native time step").  Both entry points
  * evaluate the reference's formulas as written in float64 from the float32 inputs and round every output once. */
 typedef struct { float dt, mass, g; float I[9]; } ngp_filter_dyn_t;   /* Agent's cfg (agent_helpers.py:56-61); I row-major */

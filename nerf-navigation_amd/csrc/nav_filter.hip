@@ -12,6 +12,10 @@
 // k_filter_hessian; nf_begin and nf_measure are the host side the two loop entry points have in common; the Adam step and the wave sum are the
 // planner's too (ngp_nav_step.h: ngp_adam_step, ngp_wave_sum); the axis matrices and the 3 x 3 product are ngp_filter_step.h's, at T = float.
 //
+// Multi-start (DESIGN.md §3.5 "Multi-start pose filter"): K hypotheses of B rays as ONE sequence of five launches over K B rays.  k_filter_rays_multi,
+// k_filter_loss_multi and k_filter_step_multi give hypothesis k (blockIdx.y, or blockIdx.x of the step) the slice [k B, (k + 1) B) of every per-ray buffer
+// and run the bodies the single kernels run (nf_ray_of, nf_squared_error, nf_step), so row k is the single run from the same start bit for bit.
+//
 // The derivative conventions are torch autograd's of the formula as written (nav/math_utils.py:159-174): R = I + sin(a) K + ((1 - cos(a)) K) K,
 // K = hat(r / (1e-10 + a)), a = |r|, with the denominator's dependence on a kept and a zero subgradient of the norm at r = 0.  No gradient flows through
 // near / far (nerf/renderer.py:140-141).  No atomics; every sum runs in a fixed order, so two runs are bit-identical.
@@ -191,11 +195,9 @@ __device__ __forceinline__ float nf_loss(const nf_shared& S) {
 // device
 // ---------------------------------------------------------------------------
 
-__global__ __launch_bounds__(NF_THREADS) void k_filter_rays(nf_view V, const float* __restrict__ state, const int32_t* __restrict__ batch, uint32_t B,
-                                                            float* __restrict__ rays_o, float* __restrict__ rays_d, float* __restrict__ nears,
-                                                            float* __restrict__ fars) {
-    const uint32_t n = blockIdx.x * NF_THREADS + threadIdx.x;
-    if (n >= B) return;
+// ray n of the batch from `state`: the body of k_filter_rays and k_filter_rays_multi (the pointers are the hypothesis' own slices)
+__device__ __forceinline__ void nf_ray_of(const nf_view& V, const float* __restrict__ state, const int32_t* __restrict__ batch, uint32_t n,
+                                          float* __restrict__ rays_o, float* __restrict__ rays_d, float* __restrict__ nears, float* __restrict__ fars) {
     float x[12];
 #pragma unroll
     for (int k = 0; k < 12; k++) x[k] = state[k];
@@ -214,10 +216,29 @@ __global__ __launch_bounds__(NF_THREADS) void k_filter_rays(nf_view V, const flo
     nears[n] = near; fars[n] = far;
 }
 
-__global__ __launch_bounds__(NF_THREADS) void k_filter_loss(const float* __restrict__ image, const float* __restrict__ target,
-                                                            const int32_t* __restrict__ batch, uint32_t B, uint32_t H, uint32_t W,
-                                                            float* __restrict__ grad_image, float* __restrict__ partials) {
-    __shared__ float wave_sums[NF_WAVES];
+__global__ __launch_bounds__(NF_THREADS) void k_filter_rays(nf_view V, const float* __restrict__ state, const int32_t* __restrict__ batch, uint32_t B,
+                                                            float* __restrict__ rays_o, float* __restrict__ rays_d, float* __restrict__ nears,
+                                                            float* __restrict__ fars) {
+    const uint32_t n = blockIdx.x * NF_THREADS + threadIdx.x;
+    if (n >= B) return;
+    nf_ray_of(V, state, batch, n, rays_o, rays_d, nears, fars);
+}
+
+// grid (ceil(B / 256), K): hypothesis k = blockIdx.y writes rays [k B, (k + 1) B) from states[k]; the batch is shared
+__global__ __launch_bounds__(NF_THREADS) void k_filter_rays_multi(nf_view V, const float* __restrict__ states, const int32_t* __restrict__ batch, uint32_t B,
+                                                                  float* __restrict__ rays_o, float* __restrict__ rays_d, float* __restrict__ nears,
+                                                                  float* __restrict__ fars) {
+    const uint32_t n = blockIdx.x * NF_THREADS + threadIdx.x;
+    if (n >= B) return;
+    const size_t first = (size_t)blockIdx.y * B;
+    nf_ray_of(V, states + 12 * (size_t)blockIdx.y, batch, n, rays_o + 3 * first, rays_d + 3 * first, nears + first, fars + first);
+}
+
+// one workgroup's 256 rays of a batch of B: grad_image = 2 (rgb - target) / (3 B) and the workgroup's sum of the squared error into *partial; the body of
+// k_filter_loss and k_filter_loss_multi (image and grad_image are the hypothesis' own slices, B is ITS ray count: mse_loss's mean is per hypothesis)
+__device__ __forceinline__ void nf_squared_error(float* wave_sums, const float* __restrict__ image, const float* __restrict__ target,
+                                                 const int32_t* __restrict__ batch, uint32_t B, uint32_t H, uint32_t W, float* __restrict__ grad_image,
+                                                 float* __restrict__ partial) {
     const uint32_t n = blockIdx.x * NF_THREADS + threadIdx.x;
     float sq = 0.0f;
     if (n < B) {
@@ -240,16 +261,32 @@ __global__ __launch_bounds__(NF_THREADS) void k_filter_loss(const float* __restr
         float s = wave_sums[0];
 #pragma unroll
         for (uint32_t w = 1; w < NF_WAVES; w++) s += wave_sums[w];
-        partials[blockIdx.x] = s;
+        *partial = s;
     }
 }
 
-__global__ __launch_bounds__(NF_THREADS) void k_filter_step(nf_view V, nf_step_args A, int update, float* __restrict__ state, float* __restrict__ adam,
-                                                            const int32_t* __restrict__ batch, uint32_t B, const float* __restrict__ grad_rays_o,
-                                                            const float* __restrict__ grad_rays_d, const float* __restrict__ partials,
-                                                            uint32_t n_partials, float* __restrict__ loss_out, float* __restrict__ state_out,
-                                                            float* __restrict__ grad_out) {
-    __shared__ nf_shared S;
+__global__ __launch_bounds__(NF_THREADS) void k_filter_loss(const float* __restrict__ image, const float* __restrict__ target,
+                                                            const int32_t* __restrict__ batch, uint32_t B, uint32_t H, uint32_t W,
+                                                            float* __restrict__ grad_image, float* __restrict__ partials) {
+    __shared__ float wave_sums[NF_WAVES];
+    nf_squared_error(wave_sums, image, target, batch, B, H, W, grad_image, partials + blockIdx.x);
+}
+
+// grid (ceil(B / 256), K): hypothesis k = blockIdx.y takes image rows [k B, (k + 1) B) and writes partials[k gridDim.x + blockIdx.x]
+__global__ __launch_bounds__(NF_THREADS) void k_filter_loss_multi(const float* __restrict__ image, const float* __restrict__ target,
+                                                                  const int32_t* __restrict__ batch, uint32_t B, uint32_t H, uint32_t W,
+                                                                  float* __restrict__ grad_image, float* __restrict__ partials) {
+    __shared__ float wave_sums[NF_WAVES];
+    const size_t first = 3 * (size_t)blockIdx.y * B;
+    nf_squared_error(wave_sums, image + first, target, batch, B, H, W, grad_image + first, partials + (size_t)blockIdx.y * gridDim.x + blockIdx.x);
+}
+
+// one workgroup, one hypothesis: the passes over its rays, gradients and partials, the records and the Adam step; the body of k_filter_step and
+// k_filter_step_multi
+__device__ __forceinline__ void nf_step(nf_shared& S, const nf_view& V, const nf_step_args& A, int update, float* __restrict__ state, float* __restrict__ adam,
+                                        const int32_t* __restrict__ batch, uint32_t B, const float* __restrict__ grad_rays_o,
+                                        const float* __restrict__ grad_rays_d, const float* __restrict__ partials, uint32_t n_partials,
+                                        float* __restrict__ loss_out, float* __restrict__ state_out, float* __restrict__ grad_out) {
     const uint32_t tid = threadIdx.x;
     const float step = adam[NF_STEP] + 1.0f;                                 // read before any lane writes it (there are barriers in between)
     nf_load_state(S, A, state);
@@ -280,6 +317,48 @@ __global__ __launch_bounds__(NF_THREADS) void k_filter_step(nf_view V, nf_step_a
     }
 }
 
+__global__ __launch_bounds__(NF_THREADS) void k_filter_step(nf_view V, nf_step_args A, int update, float* __restrict__ state, float* __restrict__ adam,
+                                                            const int32_t* __restrict__ batch, uint32_t B, const float* __restrict__ grad_rays_o,
+                                                            const float* __restrict__ grad_rays_d, const float* __restrict__ partials,
+                                                            uint32_t n_partials, float* __restrict__ loss_out, float* __restrict__ state_out,
+                                                            float* __restrict__ grad_out) {
+    __shared__ nf_shared S;
+    nf_step(S, V, A, update, state, adam, batch, B, grad_rays_o, grad_rays_d, partials, n_partials, loss_out, state_out, grad_out);
+}
+
+// K workgroups: workgroup k steps states[k] and adam_states[k] from rays [k B, (k + 1) B) and partials [k n_partials, (k + 1) n_partials); the records of
+// one iteration are [K] and [K,12]
+__global__ __launch_bounds__(NF_THREADS) void k_filter_step_multi(nf_view V, nf_step_args A, int update, float* __restrict__ states, float* __restrict__ adam_states,
+                                                                  const int32_t* __restrict__ batch, uint32_t B, const float* __restrict__ grad_rays_o,
+                                                                  const float* __restrict__ grad_rays_d, const float* __restrict__ partials,
+                                                                  uint32_t n_partials, float* __restrict__ loss_out, float* __restrict__ state_out,
+                                                                  float* __restrict__ grad_out) {
+    __shared__ nf_shared S;
+    const size_t k = blockIdx.x, first = 3 * k * B;
+    nf_step(S, V, A, update, states + 12 * k, adam_states + NGP_FILTER_ADAM_FLOATS * k, batch, B, grad_rays_o + first, grad_rays_d + first,
+            partials + k * n_partials, n_partials, loss_out ? loss_out + k : nullptr, state_out ? state_out + 12 * k : nullptr,
+            grad_out ? grad_out + 12 * k : nullptr);
+}
+
+// the best of K final losses, indices in ascending order: a candidate replaces the best when its loss is smaller, or when the best is NaN and the
+// candidate is not; so ties keep the lowest index and K NaNs give index 0.  One copy for the kernel and ngp_filter_select_host
+__host__ __device__ inline uint32_t nf_select(const float* losses, uint32_t K) {
+    uint32_t best = 0;
+    for (uint32_t i = 1; i < K; i++) {
+        const float l = losses[i], b = losses[best];
+        if (l < b || (b != b && l == l)) best = i;
+    }
+    return best;
+}
+
+// one wave: every lane scans the K losses (K <= 64), lanes 0-11 copy the winner's state, lane 0 its loss and index
+__global__ __launch_bounds__(64) void k_filter_select(const float* __restrict__ losses, const float* __restrict__ states, uint32_t K,
+                                                      float* __restrict__ best_state, float* __restrict__ best_loss, uint32_t* __restrict__ best_index) {
+    const uint32_t best = nf_select(losses, K);
+    if (threadIdx.x < 12) best_state[threadIdx.x] = states[12 * (size_t)best + threadIdx.x];
+    if (threadIdx.x == 0) { *best_loss = losses[best]; *best_index = best; }
+}
+
 // ---------------------------------------------------------------------------
 // host
 // ---------------------------------------------------------------------------
@@ -290,15 +369,19 @@ struct nf_ws {
     float *grad_rays_o, *grad_rays_d, *partials;
     size_t saved_bytes, total;
 };
-static nf_ws nf_layout(uint32_t B, uint32_t num_steps, void* base) {
-    if (B < 1 || B > NF_MAX_B || num_steps < 1 || num_steps > NF_MAX_T) return {};   // total 0: a shape no filter call accepts
-    const size_t n = B, kept = ngp_nav_run_saved_bytes(B, num_steps);
+// K hypotheses of B rays: every per-ray piece holds K B rays, hypothesis k in [k B, (k + 1) B), and the partials K slices of ceil(B / 256).  The pieces
+// and their order are one statement for both entry points' workspaces; K = 1 is the single loop's
+static nf_ws nf_multi_layout(uint32_t K, uint32_t B, uint32_t num_steps, void* base) {
+    if (K < 1 || K > NGP_FILTER_MULTI_MAX_K || B < 1 || (uint64_t)K * B > NF_MAX_B || num_steps < 1 || num_steps > NF_MAX_T) return {};   // total 0: a shape no filter call accepts
+    const size_t n = (size_t)K * B, kept = ngp_nav_run_saved_bytes(K * B, num_steps);
     ngp_carver c(base);
     return {c.take<float>(3 * n), c.take<float>(3 * n), c.take<float>(n), c.take<float>(n), c.take<float>(3 * n), c.take<float>(n), c.take<float>(n),
-            c.take<float>(3 * n), c.take<unsigned char>(kept), c.take<float>(3 * n), c.take<float>(3 * n), c.take<float>(ngp_div_up(B, NF_THREADS)),
-            kept, c.total(256)};
+            c.take<float>(3 * n), c.take<unsigned char>(kept), c.take<float>(3 * n), c.take<float>(3 * n),
+            c.take<float>((size_t)K * ngp_div_up(B, NF_THREADS)), kept, c.total(256)};
 }
+static nf_ws nf_layout(uint32_t B, uint32_t num_steps, void* base) { return nf_multi_layout(1, B, num_steps, base); }
 extern "C" size_t ngp_filter_workspace(uint32_t B, uint32_t num_steps) { return nf_layout(B, num_steps, nullptr).total; }
+extern "C" size_t ngp_filter_multi_workspace(uint32_t K, uint32_t B, uint32_t num_steps) { return nf_multi_layout(K, B, num_steps, nullptr).total; }
 
 static int nf_view_of(const char* who, const ngp_filter_cfg_t* c, nf_view& V) {
     NGP_REQUIRE(c, "%s: null cfg", who);
@@ -324,17 +407,18 @@ extern "C" int ngp_filter_rays(const ngp_filter_cfg_t* c, const float* state, co
 
 // what the two entry points of the loop do before they queue anything, in this order: the view, the shape, the entry point's own null-pointer refusal
 // (`null_refusal`: its message, or NULL where every pointer is there), the workspace, the field (N = 0 validates and launches nothing), and the
-// start state and inverse covariance the last kernel takes as arguments (A.adam is left zeroed)
-static int nf_begin(const char* who, const char* null_refusal, const ngp_nav_field_t* field, const void* prepared, const ngp_filter_cfg_t* c,
-                    void* workspace, size_t workspace_bytes, void* stream, nf_view& V, nf_ws& w, nf_step_args& A) {
+// start state and inverse covariance the last kernel takes as arguments (A.adam is left zeroed).  K hypotheses (1: the single loop and the Hessian) size
+// the workspace, whose size function `ws_fn` names
+static int nf_begin(const char* who, const char* null_refusal, const ngp_nav_field_t* field, const void* prepared, const ngp_filter_cfg_t* c, uint32_t K,
+                    const char* ws_fn, void* workspace, size_t workspace_bytes, void* stream, nf_view& V, nf_ws& w, nf_step_args& A) {
     const int rc_v = nf_view_of(who, c, V);
     if (rc_v != NGP_OK) return rc_v;
     const uint32_t T = c->num_steps;
     NGP_REQUIRE(T >= 1 && T <= NF_MAX_T, "%s: num_steps = %u; supported 1 <= num_steps <= 4096", who, T);
     NGP_REQUIRE(!null_refusal, "%s", null_refusal);
-    w = nf_layout(c->B, T, workspace);
+    w = nf_multi_layout(K, c->B, T, workspace);
     if (!workspace || workspace_bytes < w.total)
-        return ngp_fail(NGP_EWORKSPACE, "%s: workspace of %zu bytes, needs ngp_filter_workspace(B, num_steps) = %zu", who, workspace_bytes, w.total);
+        return ngp_fail(NGP_EWORKSPACE, "%s: workspace of %zu bytes, needs %s = %zu", who, workspace_bytes, ws_fn, w.total);
     const int rc_f = ngp_nav_run_forward(field, prepared, w.rays_o, w.rays_d, w.nears, w.fars, 0, T, c->aabb, c->bg, w.image, w.depth, w.weights_sum, w.saved,
                                          w.saved_bytes, stream);
     if (rc_f != NGP_OK) return rc_f;
@@ -349,21 +433,24 @@ static int nf_launched(const char* who, const char* what) {
     return e == hipSuccess ? NGP_OK : ngp_fail(NGP_ELAUNCH, "%s: %s: %s", who, what, hipGetErrorString(e));
 }
 
-// the measurement pass at `state` for one batch: rays -> run forward -> loss -> run backward, queued; leaves grad_rays_o, grad_rays_d and the loss partials in w
+// the measurement pass at `state` for one batch: rays -> run forward -> loss -> run backward, queued; leaves grad_rays_o, grad_rays_d and the loss partials in w.
+// K = 0: one state, the single kernels; K >= 1: `state` is [K,12] and the multi kernels fill K slices, with the run kernels launched once over K B rays
 static int nf_measure(const char* who, const ngp_nav_field_t* field, const void* prepared, const ngp_filter_cfg_t* c, const nf_view& V, const nf_ws& w,
-                      const float* state, const float* target, const int32_t* batch, void* stream) {
-    const uint32_t B = c->B, T = c->num_steps, blocks = ngp_div_up(B, NF_THREADS);
+                      uint32_t K, const float* state, const float* target, const int32_t* batch, void* stream) {
+    const uint32_t B = c->B, T = c->num_steps, blocks = ngp_div_up(B, NF_THREADS), N = (K ? K : 1u) * B;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_filter_rays, dim3(blocks), dim3(NF_THREADS), 0, s, V, state, batch, B, w.rays_o, w.rays_d, w.nears, w.fars);
+    if (K) hipLaunchKernelGGL(k_filter_rays_multi, dim3(blocks, K), dim3(NF_THREADS), 0, s, V, state, batch, B, w.rays_o, w.rays_d, w.nears, w.fars);
+    else hipLaunchKernelGGL(k_filter_rays, dim3(blocks), dim3(NF_THREADS), 0, s, V, state, batch, B, w.rays_o, w.rays_d, w.nears, w.fars);
     int rc = nf_launched(who, "rays");
     if (rc != NGP_OK) return rc;
-    rc = ngp_nav_run_forward(field, prepared, w.rays_o, w.rays_d, w.nears, w.fars, B, T, c->aabb, c->bg, w.image, w.depth, w.weights_sum, w.saved,
+    rc = ngp_nav_run_forward(field, prepared, w.rays_o, w.rays_d, w.nears, w.fars, N, T, c->aabb, c->bg, w.image, w.depth, w.weights_sum, w.saved,
                              w.saved_bytes, stream);
     if (rc != NGP_OK) return rc;
-    hipLaunchKernelGGL(k_filter_loss, dim3(blocks), dim3(NF_THREADS), 0, s, (const float*)w.image, target, batch, B, c->H, c->W, w.grad_image, w.partials);
+    if (K) hipLaunchKernelGGL(k_filter_loss_multi, dim3(blocks, K), dim3(NF_THREADS), 0, s, (const float*)w.image, target, batch, B, c->H, c->W, w.grad_image, w.partials);
+    else hipLaunchKernelGGL(k_filter_loss, dim3(blocks), dim3(NF_THREADS), 0, s, (const float*)w.image, target, batch, B, c->H, c->W, w.grad_image, w.partials);
     rc = nf_launched(who, "loss");
     if (rc != NGP_OK) return rc;
-    return ngp_nav_run_backward(field, prepared, w.rays_o, w.rays_d, w.nears, w.fars, B, T, c->aabb, c->bg, w.grad_image, nullptr, nullptr, w.saved,
+    return ngp_nav_run_backward(field, prepared, w.rays_o, w.rays_d, w.nears, w.fars, N, T, c->aabb, c->bg, w.grad_image, nullptr, nullptr, w.saved,
                                 w.saved_bytes, w.grad_rays_o, w.grad_rays_d, stream);
 }
 
@@ -374,19 +461,72 @@ extern "C" int ngp_filter_iterations(const ngp_nav_field_t* field, const void* p
     nf_ws w;
     nf_step_args A;
     int rc = nf_begin("filter_iterations", state && adam_state && target && batches ? nullptr : "filter_iterations: null state / adam_state / target / batches",
-                      field, prepared, c, workspace, workspace_bytes, stream, V, w, A);
+                      field, prepared, c, 1, "ngp_filter_workspace(B, num_steps)", workspace, workspace_bytes, stream, V, w, A);
     if (rc != NGP_OK) return rc;
     A.adam = ngp_adam_fill(c->lr, c->beta1, c->beta2, c->eps);
     const uint32_t B = c->B, blocks = ngp_div_up(B, NF_THREADS);
     for (uint32_t k = 0; k < n_iter; k++) {
         const int32_t* batch = batches + 2 * (size_t)B * ((size_t)first_iter + k);
-        rc = nf_measure("filter_iterations", field, prepared, c, V, w, state, target, batch, stream);
+        rc = nf_measure("filter_iterations", field, prepared, c, V, w, 0, state, target, batch, stream);
         if (rc != NGP_OK) return rc;
         hipLaunchKernelGGL(k_filter_step, dim3(1), dim3(NF_THREADS), 0, (hipStream_t)stream, V, A, update, state, adam_state, batch, B,
                            (const float*)w.grad_rays_o, (const float*)w.grad_rays_d, (const float*)w.partials, blocks, losses ? losses + k : (float*)nullptr,
                            states_out ? states_out + 12 * (size_t)k : (float*)nullptr, grads_out ? grads_out + 12 * (size_t)k : (float*)nullptr);
         NGP_CHECK_LAUNCH("filter_iterations: step");
     }
+    return NGP_OK;
+}
+
+extern "C" int ngp_filter_iterations_multi(const ngp_nav_field_t* field, const void* prepared, const ngp_filter_cfg_t* c, uint32_t K, float* states,
+                                           float* adam_states, const float* target, const int32_t* batches, uint32_t first_iter, uint32_t n_iter, int update,
+                                           float* losses, float* states_out, float* grads_out, void* workspace, size_t workspace_bytes, void* stream) {
+    NGP_REQUIRE(K >= 1 && K <= NGP_FILTER_MULTI_MAX_K, "filter_iterations_multi: K = %u hypotheses; supported 1 <= K <= %u", K, NGP_FILTER_MULTI_MAX_K);
+    NGP_REQUIRE(!c || c->B > NF_MAX_B || (uint64_t)K * c->B <= NF_MAX_B, "filter_iterations_multi: K * B = %u * %u rays per iteration; supported K * B <= 2^20",
+                K, c ? c->B : 0u);
+    nf_view V;
+    nf_ws w;
+    nf_step_args A;
+    int rc = nf_begin("filter_iterations_multi",
+                      states && adam_states && target && batches ? nullptr : "filter_iterations_multi: null states / adam_states / target / batches", field,
+                      prepared, c, K, "ngp_filter_multi_workspace(K, B, num_steps)", workspace, workspace_bytes, stream, V, w, A);
+    if (rc != NGP_OK) return rc;
+    A.adam = ngp_adam_fill(c->lr, c->beta1, c->beta2, c->eps);
+    const uint32_t B = c->B, blocks = ngp_div_up(B, NF_THREADS);
+    for (uint32_t k = 0; k < n_iter; k++) {
+        const int32_t* batch = batches + 2 * (size_t)B * ((size_t)first_iter + k);
+        rc = nf_measure("filter_iterations_multi", field, prepared, c, V, w, K, states, target, batch, stream);
+        if (rc != NGP_OK) return rc;
+        const size_t row = (size_t)k * K;
+        hipLaunchKernelGGL(k_filter_step_multi, dim3(K), dim3(NF_THREADS), 0, (hipStream_t)stream, V, A, update, states, adam_states, batch, B,
+                           (const float*)w.grad_rays_o, (const float*)w.grad_rays_d, (const float*)w.partials, blocks, losses ? losses + row : (float*)nullptr,
+                           states_out ? states_out + 12 * row : (float*)nullptr, grads_out ? grads_out + 12 * row : (float*)nullptr);
+        NGP_CHECK_LAUNCH("filter_iterations_multi: step");
+    }
+    return NGP_OK;
+}
+
+static int nf_select_args(const char* who, const float* losses, const float* states, uint32_t K, float* best_state, float* best_loss, uint32_t* best_index) {
+    NGP_REQUIRE(K >= 1 && K <= NGP_FILTER_MULTI_MAX_K, "%s: K = %u hypotheses; supported 1 <= K <= %u", who, K, NGP_FILTER_MULTI_MAX_K);
+    NGP_REQUIRE(losses && states && best_state && best_loss && best_index, "%s: null pointer", who);
+    return NGP_OK;
+}
+
+extern "C" int ngp_filter_select(const float* losses, const float* states, uint32_t K, float* best_state, float* best_loss, uint32_t* best_index,
+                                 void* stream) {
+    const int rc = nf_select_args("filter_select", losses, states, K, best_state, best_loss, best_index);
+    if (rc != NGP_OK) return rc;
+    hipLaunchKernelGGL(k_filter_select, dim3(1), dim3(64), 0, (hipStream_t)stream, losses, states, K, best_state, best_loss, best_index);
+    NGP_CHECK_LAUNCH("filter_select");
+    return NGP_OK;
+}
+
+extern "C" int ngp_filter_select_host(const float* losses, const float* states, uint32_t K, float* best_state, float* best_loss, uint32_t* best_index) {
+    const int rc = nf_select_args("filter_select_host", losses, states, K, best_state, best_loss, best_index);
+    if (rc != NGP_OK) return rc;
+    const uint32_t best = nf_select(losses, K);
+    for (int e = 0; e < 12; e++) best_state[e] = states[12 * (size_t)best + e];
+    *best_loss = losses[best];
+    *best_index = best;
     return NGP_OK;
 }
 
@@ -502,9 +642,9 @@ extern "C" int ngp_filter_hessian(const ngp_nav_field_t* field, const void* prep
     nf_ws w;
     nf_step_args A;
     int rc = nf_begin("filter_hessian", state && target && batch && hessian ? nullptr : "filter_hessian: null state / target / batch / hessian", field,
-                      prepared, c, workspace, workspace_bytes, stream, V, w, A);
+                      prepared, c, 1, "ngp_filter_workspace(B, num_steps)", workspace, workspace_bytes, stream, V, w, A);
     if (rc != NGP_OK) return rc;
-    rc = nf_measure("filter_hessian", field, prepared, c, V, w, state, target, batch, stream);
+    rc = nf_measure("filter_hessian", field, prepared, c, V, w, 0, state, target, batch, stream);
     if (rc != NGP_OK) return rc;
     hipLaunchKernelGGL(k_filter_hessian, dim3(1), dim3(NF_THREADS), 0, (hipStream_t)stream, V, A, state, batch, c->B, (const float*)w.grad_rays_o,
                        (const float*)w.grad_rays_d, (const float*)w.partials, ngp_div_up(c->B, NF_THREADS), hessian, grad, loss, dLdP);

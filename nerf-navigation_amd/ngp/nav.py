@@ -836,6 +836,11 @@ class NativePoseFilter:
     with one 4-byte host read (the number of pixels M).
 
         xt = filt.estimate_state(target, action, features="native", seed=7)   # the whole time step from the sensor image
+
+    For a poor prior the loop can run from K initial points at once (DESIGN 3.5 "Multi-start pose filter"): K hypotheses of the same objective in one
+    sequence of five launches per iteration, the best final objective kept on the device; hypothesis k is bit for bit the single run from its start.
+
+        xt = filt.estimate_state(target, action, interest_regions, rng=rng, offsets=offsets)   # offsets [K,12] around the propagated state
     """
 
     def __init__(self, filter_cfg, queries, start_state=None, agent_cfg=None):
@@ -857,6 +862,8 @@ class NativePoseFilter:
         self.iteration = 0
         self.hessian_grad = self.hessian_loss = self.hessian_dLdP = None
         self._feat_ws = self._seed0 = None
+        self.multi = None                                    # the hypotheses of the last multi-start run (estimate_relative_pose_multi)
+        self._ws_multi = None
 
     # -- plumbing ------------------------------------------------------------------------------------------------------
     def _vec(self, v):
@@ -1069,6 +1076,111 @@ class NativePoseFilter:
         self.batch = batches[n - 1] if n else None
         return state.detach()
 
+    # -- multi-start: K hypotheses of one objective in one launch sequence (DESIGN 3.5 "Multi-start pose filter") ---------------
+    def _workspace_multi(self, K, B):
+        import ngp_hip as _hip
+        nbytes = _hip.lib().ngp_filter_multi_workspace(int(K), int(B), int(self.queries.num_steps))
+        if nbytes == 0:
+            raise ValueError(f"{K} hypotheses of {B} rays: supported 1 <= K <= {_hip.FILTER_MULTI_MAX_K} and K * B <= 2^20")
+        if self._ws_multi is None or self._ws_multi.numel() < nbytes:
+            self._ws_multi = _hip.workspace(nbytes, self.device)
+        return self._ws_multi
+
+    def new_adam_state_multi(self, K):
+        """zeroed Adam moments and steps of K hypotheses: [K, FILTER_ADAM_FLOATS]"""
+        import ngp_hip as _hip
+        return torch.zeros(int(K), _hip.FILTER_ADAM_FLOATS, dtype=torch.float32, device=self.device)
+
+    def _iterations_multi(self, c, first_iter, n_iter, adam_states, states, target, batches, update, losses, states_out, grads):
+        """ngp_filter_iterations_multi with a ready cfg struct `c` (so that two calls in a row build it once)"""
+        import ctypes
+        import ngp_hip as _hip
+        K, B = int(states.shape[0]), int(batches.shape[1])
+        st, prep = self.queries.native.struct()
+        ws = self._workspace_multi(K, B)
+        _hip.check(_hip.lib().ngp_filter_iterations_multi(ctypes.byref(st), _hip.ptr(prep), ctypes.byref(c), K, _hip.ptr(states), _hip.ptr(adam_states),
+                                                          _hip.ptr(target), _hip.ptr(batches), int(first_iter), int(n_iter), 1 if update else 0,
+                                                          _hip.ptr(losses), _hip.ptr(states_out), _hip.ptr(grads), _hip.ptr(ws), ws.numel(), _hip.stream()),
+                   "filter_iterations_multi")
+
+    def run_iterations_multi(self, first_iter, n_iter, adam_states, states, start_state, sig, target, batches, update=True, losses=None, states_out=None,
+                             grads=None):
+        """run_iterations for K hypotheses of the same objective (one start_state as the Mahalanobis centre, one sig, one target, shared batches): 5
+        launches per iteration whatever K is.  states: contiguous float32 [K,12] on the GPU, updated in place; adam_states: [K, FILTER_ADAM_FLOATS] from
+        new_adam_state_multi; losses [n_iter,K], states_out, grads [n_iter,K,12]: device tensors or None, the values before each step.  Row k of every
+        result is bit for bit run_iterations' from states[k]."""
+        import ngp_hip as _hip
+        if not (batches.is_cuda and batches.dtype == torch.int32 and batches.is_contiguous() and batches.dim() == 3 and batches.shape[2] == 2):
+            raise ValueError("run_iterations_multi takes batches as draw_batches returns them: [n, B, 2] int32 on the GPU")
+        if int(first_iter) < 0 or int(first_iter) + int(n_iter) > batches.shape[0]:
+            raise ValueError(f"iterations {first_iter} .. {int(first_iter) + int(n_iter)} reach past the {batches.shape[0]} batches")
+        if not (states.is_cuda and states.dtype == torch.float32 and states.is_contiguous() and states.dim() == 2 and states.shape[1] == 12
+                and states.shape[0] >= 1):
+            raise ValueError("states must be a contiguous float32 [K, 12] tensor on the GPU")
+        K = int(states.shape[0])
+        if not (adam_states.is_cuda and adam_states.dtype == torch.float32 and adam_states.is_contiguous()
+                and tuple(adam_states.shape) == (K, _hip.FILTER_ADAM_FLOATS)):
+            raise ValueError(f"adam_states must be a contiguous float32 [{K}, {_hip.FILTER_ADAM_FLOATS}] tensor on the GPU (new_adam_state_multi)")
+        for name, t, shape in (("losses", losses, (n_iter, K)), ("states_out", states_out, (n_iter, K, 12)), ("grads", grads, (n_iter, K, 12))):
+            if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape):
+                raise ValueError(f"{name} must be a contiguous float32 {list(shape)} tensor on the GPU")
+        B = int(batches.shape[1])
+        self._iterations_multi(self._cfg_struct(B, start_state, sig), first_iter, n_iter, adam_states, states, self._target(target), batches, update,
+                               losses, states_out, grads)
+
+    def select(self, losses, states):
+        """ngp_filter_select: the hypothesis with the best loss, on the device -> (state [12], loss [1], index [1] int32).  Indices are scanned in ascending
+        order; a candidate replaces the best when its loss is smaller, or when the best is NaN and the candidate is not: ties keep the lowest index, K
+        NaNs give index 0.  One launch, no host read."""
+        import ngp_hip as _hip
+        losses, states = losses.contiguous(), states.contiguous()
+        K = int(losses.numel())
+        if not (losses.is_cuda and losses.dtype == torch.float32 and states.is_cuda and states.dtype == torch.float32 and tuple(states.shape) == (K, 12)):
+            raise ValueError("select takes float32 losses [K] and states [K, 12] on the GPU")
+        best = torch.empty(12, dtype=torch.float32, device=self.device)
+        loss = torch.empty(1, dtype=torch.float32, device=self.device)
+        index = torch.empty(1, dtype=torch.int32, device=self.device)           # the C side writes a uint32 <= 63
+        _hip.check(_hip.lib().ngp_filter_select(_hip.ptr(losses), _hip.ptr(states), K, _hip.ptr(best), _hip.ptr(loss), _hip.ptr(index), _hip.stream()),
+                   "filter_select")
+        return best, loss, index
+
+    def estimate_relative_pose_multi(self, target, start_state, sig, batches, offsets, check=True):
+        """estimate_relative_pose from K initial points (start_state + offsets[k]) + 1e-6, offsets [K,12]: all K minimise the same objective (start_state
+        stays the Mahalanobis centre) over the same batches, N_iter iterations with fresh moments in one call; then one more measurement pass
+        (update = 0) on the last batch -- the batch the Hessian will use -- gives every hypothesis' final objective, and ngp_filter_select picks the
+        winner (rule: `select`).  Returns the winner's state [12].  Keeps multi = dict(states [K,12], final_losses [K], index [1] int32, losses
+        [N_iter,K], states_hist, grads [N_iter,K,12]) and, gathered on the device with the index tensor, the winner's losses, states and grads; target
+        and the last batch as the single route does.  Nothing of the results is read to the host: the winner's index stays on the device.  A zero
+        row of offsets is exactly estimate_relative_pose's run."""
+        n = self.iter
+        if n < 1:
+            raise ValueError("estimate_relative_pose_multi compares the hypotheses on the last iteration's batch: N_iter must be at least 1")
+        batches = self._batches(batches, check)
+        if batches.shape[0] < n:
+            raise ValueError(f"{n} iterations need {n} batches, got {batches.shape[0]}")
+        target = self._target(target)
+        offsets = torch.as_tensor(offsets).detach().to(self.device, torch.float32)
+        if offsets.dim() != 2 or offsets.shape[1] != 12 or offsets.shape[0] < 1:
+            raise ValueError("offsets must be [K, 12]")
+        K = int(offsets.shape[0])
+        states = ((self._vec(start_state)[None] + offsets) + 1e-6).contiguous()
+        kw = dict(dtype=torch.float32, device=self.device)
+        losses, hist, grads = torch.empty(n, K, **kw), torch.empty(n, K, 12, **kw), torch.empty(n, K, 12, **kw)
+        final = torch.empty(1, K, **kw)
+        adam = self.new_adam_state_multi(K)
+        c = self._cfg_struct(int(batches.shape[1]), start_state, sig)
+        self._iterations_multi(c, 0, n, adam, states, target, batches, True, losses, hist, grads)
+        self._iterations_multi(c, n - 1, 1, adam, states, target, batches, False, final, None, None)
+        best, _, index = self.select(final[0], states)
+        pick = index.long()
+        self.multi = dict(states=states, final_losses=final[0], index=index, losses=losses, states_hist=hist, grads=grads)
+        self.losses = losses.index_select(1, pick).reshape(n)
+        self.states = hist.index_select(1, pick).reshape(n, 12)
+        self.grads = grads.index_select(1, pick).reshape(n, 12)
+        self.target = target
+        self.batch = batches[n - 1]
+        return best
+
     def measurement_fn(self, state, start_state, sig, target, batch):
         """Estimator.measurement_fn (nav/estimator_helpers.py:293-327) in torch over the queries (differentiable; the Hessian's route)"""
         delta = state - start_state
@@ -1142,7 +1254,7 @@ class NativePoseFilter:
                                                    _hip.ptr(out["A"]), _hip.ptr(out["sig_prop"]), _hip.stream()), "filter_propagate")
         return out
 
-    def estimate_state(self, target, action, interest_regions=None, batches=None, rng=None, features=None, seed=None):
+    def estimate_state(self, target, action, interest_regions=None, batches=None, rng=None, features=None, seed=None, offsets=None):
         """Estimator.estimate_state (nav/estimator_helpers.py:347-406): propagate the estimate and its covariance through the dynamics, run the loop from
         there, take the Hessian at the result and make its nearest positive-definite matrix's inverse the new covariance.  target: the sensor image,
         float32 [H,W,3] on the GPU; the loop's batches are drawn from `interest_regions` ([M,2] (row, col) pairs, with `rng`, a numpy Generator) unless
@@ -1151,8 +1263,12 @@ class NativePoseFilter:
         state_estimate, iteration.  One difference from the reference: A is the Jacobian at the previous estimate (the point the dynamics are evaluated
         at, one launch), where :362 evaluates it at the propagated one.
         features="native": the regions come from `target` itself (interest_regions) and the batches from draw_batches_native with step_seed(seed); no
-        pixel of the front is computed on the host.  No keypoint at all is the "feature detection failed" path."""
+        pixel of the front is computed on the host.  No keypoint at all is the "feature detection failed" path.
+        offsets [K,12]: the loop is the multi-start one around the propagated state (estimate_relative_pose_multi: K hypotheses in one launch sequence,
+        the best final objective wins); the Hessian and the covariance are taken at the winner, everything else about the time step is unchanged.
+        A zero row is today's single start."""
         import numpy as np
+        self.multi = None
         if self.xt is None:
             raise ValueError("estimate_state needs the estimate of the previous time step: NativePoseFilter(filter_cfg, queries, start_state, agent_cfg)")
         if features is not None:
@@ -1174,7 +1290,10 @@ class NativePoseFilter:
             self.losses, self.states = [], []
             xt = xt_prop.clone()
         else:
-            xt = self.estimate_relative_pose(target, xt_prop, sig_prop, batches, check=features is None)
+            if offsets is None:
+                xt = self.estimate_relative_pose(target, xt_prop, sig_prop, batches, check=features is None)
+            else:
+                xt = self.estimate_relative_pose_multi(target, xt_prop, sig_prop, batches, offsets, check=features is None)
             hess = self.measurement_hessian(xt, xt_prop, sig_prop, native=True)
             self.sig = self.covariance(hess).float().to(self.device)
         self.xt = xt
@@ -1184,11 +1303,15 @@ class NativePoseFilter:
         return xt.clone()
 
     def save_data(self, filename):
-        """Estimator.save_data (nav/estimator_helpers.py:408-419): the last time step as JSON under the reference's keys"""
+        """Estimator.save_data (nav/estimator_helpers.py:408-419): the last time step as JSON under the reference's keys (after a multi-start step: filled
+        from the winner, plus "hypotheses": the K final losses and the winning index)"""
         import json
         as_list = lambda v: v.detach().cpu().tolist() if isinstance(v, torch.Tensor) else v      # noqa: E731
         data = {"loss": as_list(self.losses), "covariance": self.covariance_estimate, "state_estimate": self.state_estimate,
                 "grad_states": as_list(self.states), "action": self.action}
+        multi = getattr(self, "multi", None)
+        if multi is not None:
+            data["hypotheses"] = {"final_losses": as_list(multi["final_losses"]), "index": int(multi["index"])}
         with open(filename, "w+") as f:
             json.dump(data, f, indent=4)
 
@@ -1372,7 +1495,8 @@ class NativeAgent:
 SIMULATE_FOLDERS = ("init_poses", "init_costs", "replan_poses", "replan_costs", "estimator_data")
 
 
-def simulate(planner_cfg, agent_cfg, filter_cfg, extra_cfg, queries, sensor=None, basefolder=None, generator=None, interest_regions=None, seed=None):
+def simulate(planner_cfg, agent_cfg, filter_cfg, extra_cfg, queries, sensor=None, basefolder=None, generator=None, interest_regions=None, seed=None,
+             filter_offsets=None):
     """simulate.simulate (simulate.py:18-102) over the native planner, agent and filter: A* and learn_init, then per MPC step the planner's action, the agent's
     noisy step and observation, the filter's time step and, before `steps - 5`, update_state and learn_update.
 
@@ -1381,6 +1505,7 @@ def simulate(planner_cfg, agent_cfg, filter_cfg, extra_cfg, queries, sensor=None
     device `generator` belongs to).  generator: torch.normal's, for the process noise.  The filter finds its regions in the observation
     (features="native", the draw keyed by `seed`) unless interest_regions ([M,2] (row, col)) are given, which are then used every step with
     numpy's default_rng(seed).  seed also seeds a_star_init's path noise; None leaves all three to the global / operating-system sources, as the reference.
+    filter_offsets [K,12]: every time step of the filter is the multi-start one (estimate_state's `offsets`); None: the loop as it is.
     basefolder: a directory (created when missing) that receives the reference's five sub-folders, init_* and replan_* from the planner, estimator_data/
     step{n}.json from the filter and true_states.json from the agent; None: nothing touches the disk.  Never prompts.
     -> dict(true_states [steps+1,12], estimates [steps,12], actions [steps,4], noises [steps,12] on the device; planner, agent, filter)."""
@@ -1414,9 +1539,9 @@ def simulate(planner_cfg, agent_cfg, filter_cfg, extra_cfg, queries, sensor=None
         noise = torch.normal(noise_mean, noise_std, generator=generator)
         agent.step(action, noise=noise)
         if interest_regions is None:
-            state_est = filt.estimate_state(agent.target, action, features="native", seed=seed)
+            state_est = filt.estimate_state(agent.target, action, features="native", seed=seed, offsets=filter_offsets)
         else:
-            state_est = filt.estimate_state(agent.target, action, interest_regions, rng=rng)
+            state_est = filt.estimate_state(agent.target, action, interest_regions, rng=rng, offsets=filter_offsets)
         if basefolder is not None:
             filt.save_data(basefolder / "estimator_data" / f"step{filt.iteration - 1}.json")
         estimates[it], actions[it], noises[it] = state_est, action, noise.to(**kw)

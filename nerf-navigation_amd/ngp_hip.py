@@ -146,6 +146,10 @@ _SIGNATURES = {
     "ngp_filter_workspace": (c_sz, [c_u32, c_u32]),
     "ngp_filter_iterations": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_u32, c_u32, c_int, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "ngp_filter_rays": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "ngp_filter_multi_workspace": (c_sz, [c_u32, c_u32, c_u32]),
+    "ngp_filter_iterations_multi": (c_int, [c_vp, c_vp, c_vp, c_u32, c_vp, c_vp, c_vp, c_vp, c_u32, c_u32, c_int, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "ngp_filter_select": (c_int, [c_vp, c_vp, c_u32, c_vp, c_vp, c_vp, c_vp]),
+    "ngp_filter_select_host": (c_int, [c_vp, c_vp, c_u32, c_vp, c_vp, c_vp]),
     "ngp_filter_propagate": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "ngp_filter_hessian": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "ngp_features_default_cfg": (None, [c_vp]),
@@ -223,6 +227,7 @@ class ngp_features_cfg_t(ctypes.Structure):
 
 
 FILTER_ADAM_FLOATS = 37                                      # include/ngp_hip.h: NGP_FILTER_ADAM_FLOATS
+FILTER_MULTI_MAX_K = 64                                      # include/ngp_hip.h: NGP_FILTER_MULTI_MAX_K
 
 
 def build(verbose=False):
