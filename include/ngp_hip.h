@@ -680,6 +680,33 @@ int ngp_plan_epochs(const ngp_nav_field_t* field_host, const void* prepared, con
                     uint32_t first_epoch, uint32_t n_epochs, int update, float* losses, float* per_state,
                     void* workspace, size_t workspace_bytes, void* stream);
 
+/* Multi-start (DESIGN.md §3.5 "Multi-start planner"): K hypotheses minimise ONE objective -- one cfg_host (start, end, dynamics, fade-out, Adam's
+ * constants) and one body -- from K initial trajectories, as one sequence of three launches per epoch whatever K is: hypothesis k owns points
+ * [k S B, (k + 1) S B) of a K S B-point density query.  Row k of every output is bit for bit what ngp_plan_epochs gives from states[k],
+ * initial_accel[k], adam_states[k], for update 1 and 0. */
+#define NGP_PLAN_MULTI_MAX_K 64u
+/* bytes of the workspace of ngp_plan_epochs_multi: the pieces of ngp_plan_workspace for K S B points; at K = 1 the same size.  0 outside 1 <= K <= 64,
+ * K (R + 3) B <= 2^26, and the R, B of ngp_plan_workspace. */
+size_t ngp_plan_multi_workspace(uint32_t K, uint32_t R, uint32_t B);
+/* n_epochs epochs of K hypotheses: 3 launches per epoch on `stream`, no synchronisation, no host read.  states [K,R,4], initial_accel [K,2] and
+ * adam_states [K,NGP_PLAN_ADAM_FLOATS(R)] are updated in place; body, first_epoch, update as for ngp_plan_epochs.  losses [n_epochs,K] (may be NULL):
+ * total_cost() of every hypothesis before each step; per_state [K,2,S] (may be NULL): per-state cost and collision * 1e6 of the last epoch.
+ * Refused on the host before anything is queued: K = 0, K > 64, K S B > 2^26, whatever ngp_plan_epochs refuses, and (NGP_EWORKSPACE) a null workspace
+ * or one shorter than ngp_plan_multi_workspace(K, R, B); then the field, for any n_epochs. */
+int ngp_plan_epochs_multi(const ngp_nav_field_t* field_host, const void* prepared, const ngp_plan_cfg_t* cfg_host, uint32_t K,
+                          float* states, float* initial_accel, float* adam_states, const float* body, uint32_t B, uint32_t R,
+                          uint32_t first_epoch, uint32_t n_epochs, int update, float* losses, float* per_state,
+                          void* workspace, size_t workspace_bytes, void* stream);
+/* The hypothesis with the best loss: ONE launch of one workgroup, no host read.  losses [K], states [K,R,4], initial_accel [K,2] -> best_states [R,4],
+ * best_accel [2], best_loss [1], best_index [1].  The rule is ngp_filter_select's (one copy, csrc/ngp_select.h): indices are scanned in ascending order
+ * from best = 0; candidate i replaces the best when losses[i] < losses[best], or when losses[best] is NaN and losses[i] is not.
+ * 1 <= K <= 64, 2 <= R <= 255, no null pointer. */
+int ngp_plan_select(const float* losses, const float* states, const float* initial_accel, uint32_t K, uint32_t R, float* best_states,
+                    float* best_accel, float* best_loss, uint32_t* best_index, void* stream);
+/* The same function compiled for the host (all pointers host memory): the rule, testable without a device. */
+int ngp_plan_select_host(const float* losses, const float* states, const float* initial_accel, uint32_t K, uint32_t R, float* best_states,
+                         float* best_accel, float* best_loss, uint32_t* best_index);
+
 /* The planner's A* initialisation (Planner.a_star_init, nav/quad_plot.py:64-115; csrc/nav_astar.hip, DESIGN.md §3.5 "Native A* initialisation").
  *
  * Occupancy: density_fn over the lattice axis_x x axis_y x axis_z (device float32 [side] each), MaxPool3d(kernel) and `> threshold` in one launch.

@@ -23,6 +23,7 @@
 #include "ngp_camera.h"
 #include "ngp_filter_step.h"
 #include "ngp_filter_pose.h"                                                 // NF_C90, nf_rodrigues, nf_rotation, nf_pose: shared with nav_agent.hip
+#include "ngp_select.h"                                                      // ngp_select_best: the selection rule, shared with nav_plan.hip
 
 static constexpr uint32_t NF_THREADS = 256, NF_WAVES = NF_THREADS / 64;
 static constexpr uint32_t NF_MAX_B = 1u << 20, NF_MAX_T = 4096;             // num_steps: what ngp_nav_run_forward accepts
@@ -340,21 +341,10 @@ __global__ __launch_bounds__(NF_THREADS) void k_filter_step_multi(nf_view V, nf_
             grad_out ? grad_out + 12 * k : nullptr);
 }
 
-// the best of K final losses, indices in ascending order: a candidate replaces the best when its loss is smaller, or when the best is NaN and the
-// candidate is not; so ties keep the lowest index and K NaNs give index 0.  One copy for the kernel and ngp_filter_select_host
-__host__ __device__ inline uint32_t nf_select(const float* losses, uint32_t K) {
-    uint32_t best = 0;
-    for (uint32_t i = 1; i < K; i++) {
-        const float l = losses[i], b = losses[best];
-        if (l < b || (b != b && l == l)) best = i;
-    }
-    return best;
-}
-
-// one wave: every lane scans the K losses (K <= 64), lanes 0-11 copy the winner's state, lane 0 its loss and index
+// one wave: every lane scans the K losses (K <= 64) by the rule of ngp_select.h, lanes 0-11 copy the winner's state, lane 0 its loss and index
 __global__ __launch_bounds__(64) void k_filter_select(const float* __restrict__ losses, const float* __restrict__ states, uint32_t K,
                                                       float* __restrict__ best_state, float* __restrict__ best_loss, uint32_t* __restrict__ best_index) {
-    const uint32_t best = nf_select(losses, K);
+    const uint32_t best = ngp_select_best(losses, K);
     if (threadIdx.x < 12) best_state[threadIdx.x] = states[12 * (size_t)best + threadIdx.x];
     if (threadIdx.x == 0) { *best_loss = losses[best]; *best_index = best; }
 }
@@ -523,7 +513,7 @@ extern "C" int ngp_filter_select(const float* losses, const float* states, uint3
 extern "C" int ngp_filter_select_host(const float* losses, const float* states, uint32_t K, float* best_state, float* best_loss, uint32_t* best_index) {
     const int rc = nf_select_args("filter_select_host", losses, states, K, best_state, best_loss, best_index);
     if (rc != NGP_OK) return rc;
-    const uint32_t best = nf_select(losses, K);
+    const uint32_t best = ngp_select_best(losses, K);
     for (int e = 0; e < 12; e++) best_state[e] = states[12 * (size_t)best + e];
     *best_loss = losses[best];
     *best_index = best;

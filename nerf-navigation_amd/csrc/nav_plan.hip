@@ -15,7 +15,12 @@
 // contracts it with the adjoints.  The derivative conventions are torch autograd's (nav/math_utils.py:115-156): the linearised acos with
 // its float32 slope, the 1 / (2 sin(ang + 1e-10)) factor, no gradient through a zero angle, zero gradient of the norm of a zero vector.
 // No atomics; every sum runs in a fixed order, so two runs are bit-identical.
+//
+// Multi-start (DESIGN.md §3.5 "Multi-start planner"): ngp_plan_epochs_multi runs K trajectories of one objective as the SAME three launches per epoch.  The two
+// one-workgroup kernels take a grid of K and workgroup k works on row k of every per-hypothesis buffer; the density query runs once over K S B points, each
+// computed in its own lane.  So row k is the single run from the same start bit for bit.  k_plan_select keeps the best by the rule of ngp_select.h.
 #include "ngp_nav_step.h"
+#include "ngp_select.h"                                                   // ngp_select_best: the multi-start selection rule, shared with nav_filter.hip
 
 #define NP_HD __host__ __device__ __forceinline__
 
@@ -397,9 +402,13 @@ __device__ void np_forward(const np_args& A, const float* __restrict__ states, c
     __syncthreads();
 }
 
-__global__ __launch_bounds__(NP_K1_THREADS) void k_plan_kinematics(np_args A, const float* __restrict__ states, const float* __restrict__ ia,
-                                                                   const float* __restrict__ body, float* __restrict__ full,
-                                                                   float* __restrict__ actions, float* __restrict__ points) {
+// Both kernels serve one hypothesis per workgroup: workgroup k = blockIdx.x owns row k of every per-hypothesis buffer (states [K,R,4], initial_accel
+// [K,2], adam [K,3P+1], points [K,S*B,3], sigma [K,S*B], jac [K,S*B,3], loss [K], per_state [K,2,S], full [K,S,18], actions [K,S,4]): the kernels offset the
+// pointers (in size_t) and run the bodies np_kinematics / np_cost_step, which keep their __restrict__ arguments.  The single entry points launch a grid of 1,
+// where every offset is zero.
+__device__ __forceinline__ void np_kinematics(const np_args& A, const float* __restrict__ states, const float* __restrict__ ia,
+                                              const float* __restrict__ body, float* __restrict__ full, float* __restrict__ actions,
+                                              float* __restrict__ points) {
     extern __shared__ float rows[];
     np_forward(A, states, ia, rows);
     const uint32_t tid = threadIdx.x, NT = blockDim.x;
@@ -419,10 +428,16 @@ __global__ __launch_bounds__(NP_K1_THREADS) void k_plan_kinematics(np_args A, co
         for (uint32_t e = tid; e < 3 * A.S * A.B; e += NT) points[e] = np_point(A, rows, body, e);
 }
 
-__global__ __launch_bounds__(NP_K3_THREADS) void k_plan_cost_step(np_args Aarg, uint32_t epoch, int update, float* __restrict__ states,
-                                                                  float* __restrict__ ia, float* __restrict__ adam, const float* __restrict__ body,
-                                                                  const float* __restrict__ sigma, const float* __restrict__ jac,
-                                                                  float* __restrict__ loss, float* __restrict__ per_state) {
+__global__ __launch_bounds__(NP_K1_THREADS) void k_plan_kinematics(np_args A, const float* states, const float* ia, const float* body, float* full,
+                                                                   float* actions, float* points) {
+    const size_t k = blockIdx.x;
+    np_kinematics(A, states + k * 4 * (size_t)A.R, ia + k * 2, body, full ? full + k * 18 * (size_t)A.S : nullptr,
+                  actions ? actions + k * 4 * (size_t)A.S : nullptr, points ? points + k * 3 * (size_t)A.S * A.B : nullptr);
+}
+
+__device__ __forceinline__ void np_cost_step(const np_args& Aarg, uint32_t epoch, int update, float* __restrict__ states, float* __restrict__ ia,
+                                             float* __restrict__ adam, const float* __restrict__ body, const float* __restrict__ sigma,
+                                             const float* __restrict__ jac, float* __restrict__ loss, float* __restrict__ per_state) {
     extern __shared__ float rows[];
     __shared__ np_args A;                                                 // the arguments from LDS: held in SGPRs they spill
     const uint32_t tid = threadIdx.x, NT = blockDim.x, P = 4 * Aarg.R + 2;
@@ -494,19 +509,32 @@ __global__ __launch_bounds__(NP_K3_THREADS) void k_plan_cost_step(np_args Aarg, 
     if (update && tid == 0) adam[3 * P] = step;
 }
 
+__global__ __launch_bounds__(NP_K3_THREADS) void k_plan_cost_step(np_args A, uint32_t epoch, int update, float* states, float* ia, float* adam,
+                                                                  const float* body, const float* sigma, const float* jac, float* loss, float* per_state) {
+    const size_t k = blockIdx.x, M = (size_t)A.S * A.B, P = 4 * (size_t)A.R + 2;
+    np_cost_step(A, epoch, update, states + k * 4 * (size_t)A.R, ia + k * 2, adam + k * (3 * P + 1), body, sigma + k * M, jac + k * 3 * M,
+                 loss ? loss + k : nullptr, per_state ? per_state + k * 2 * (size_t)A.S : nullptr);
+}
+
 // ---------------------------------------------------------------------------
 // host
 // ---------------------------------------------------------------------------
 
 // workspace (256-byte aligned pieces): body points of every state [(R + 3) B][3] | their density | its Jacobian [..][3]
+// K hypotheses: the same three pieces for K (R + 3) B points, hypothesis k in [k S B, (k + 1) S B); one statement for both entry points, K = 1 is the single loop's.
+// K S B <= 2^26 keeps the point count and the kernels' 3x element indices inside uint32_t (every R, B of the single path passes at K = 1: 258 * 65536 < 2^25)
 struct np_ws { float* points; float* sigma; float* jac; size_t total; };
-static np_ws np_layout(uint32_t R, uint32_t B, void* base) {
-    if (R < NP_MIN_R || R > NP_MAX_R || B < 1 || B > NP_MAX_B) return {};          // total 0: a shape no planner call accepts
-    const size_t n = (size_t)(R + 3) * B;
+static constexpr uint64_t NP_MAX_POINTS = 1ull << 26;
+static np_ws np_multi_layout(uint32_t K, uint32_t R, uint32_t B, void* base) {
+    if (K < 1 || K > NGP_PLAN_MULTI_MAX_K || R < NP_MIN_R || R > NP_MAX_R || B < 1 || B > NP_MAX_B || (uint64_t)K * (R + 3) * B > NP_MAX_POINTS)
+        return {};                                                                 // total 0: a shape no planner call accepts
+    const size_t n = (size_t)K * (R + 3) * B;
     ngp_carver c(base);
     return {c.take<float>(3 * n), c.take<float>(n), c.take<float>(3 * n), c.total(256)};
 }
+static np_ws np_layout(uint32_t R, uint32_t B, void* base) { return np_multi_layout(1, R, B, base); }
 extern "C" size_t ngp_plan_workspace(uint32_t R, uint32_t B) { return np_layout(R, B, nullptr).total; }
+extern "C" size_t ngp_plan_multi_workspace(uint32_t K, uint32_t R, uint32_t B) { return np_multi_layout(K, R, B, nullptr).total; }
 
 static int np_fill(const char* who, const ngp_plan_cfg_t* c, uint32_t R, uint32_t B, np_args& A) {
     NGP_REQUIRE(c, "%s: null cfg", who);
@@ -554,18 +582,17 @@ extern "C" int ngp_plan_kinematics(const ngp_plan_cfg_t* cfg, const float* state
     return NGP_OK;
 }
 
-extern "C" int ngp_plan_epochs(const ngp_nav_field_t* field, const void* prepared, const ngp_plan_cfg_t* cfg, float* states,
-                               float* initial_accel, float* adam_state, const float* body, uint32_t B, uint32_t R, uint32_t first_epoch,
-                               uint32_t n_epochs, int update, float* losses, float* per_state, void* workspace, size_t workspace_bytes,
-                               void* stream) {
-    np_args A;
-    const int rc = np_fill("plan_epochs", cfg, R, B, A);
-    if (rc != NGP_OK) return rc;
-    NGP_REQUIRE(states && initial_accel && adam_state && body, "plan_epochs: null pointer");
-    const np_ws w = np_layout(R, B, workspace);
+// the loop of both entry points, after the shape (A) has been accepted: the null-pointer refusal, the workspace (whose size function `ws_fn` names), the
+// field, then per epoch three launches whatever K is -- the kinematics and the cost step with a grid of K, the density query once over K S B points.
+// losses [n_epochs,K], per_state [K,2,S]
+static int np_epochs(const char* who, const char* ws_fn, const np_args& A, const ngp_nav_field_t* field, const void* prepared, const ngp_plan_cfg_t* cfg,
+                     uint32_t K, float* states, float* initial_accel, float* adam_states, const float* body, uint32_t first_epoch, uint32_t n_epochs,
+                     int update, float* losses, float* per_state, void* workspace, size_t workspace_bytes, void* stream) {
+    NGP_REQUIRE(states && initial_accel && adam_states && body, "%s: null pointer", who);
+    const np_ws w = np_multi_layout(K, A.R, A.B, workspace);
     if (!workspace || workspace_bytes < w.total)
-        return ngp_fail(NGP_EWORKSPACE, "plan_epochs: workspace of %zu bytes, needs ngp_plan_workspace(R, B) = %zu", workspace_bytes, w.total);
-    const uint32_t M = A.S * B;
+        return ngp_fail(NGP_EWORKSPACE, "%s: workspace of %zu bytes, needs %s = %zu", who, workspace_bytes, ws_fn, w.total);
+    const uint32_t M = K * A.S * A.B;                                      // <= 2^26 (np_multi_layout)
     float* points = w.points, *sigma = w.sigma, *jac = w.jac;
     {   // the field is checked here, before anything is queued (M = 0 validates and launches nothing)
         const int rc_f = ngp_nav_density_value_jac(field, prepared, points, 0, cfg->rot, sigma, jac, stream);
@@ -575,15 +602,84 @@ extern "C" int ngp_plan_epochs(const ngp_nav_field_t* field, const void* prepare
     { const int rc_lds = np_allow_lds(); if (rc_lds != NGP_OK) return rc_lds; }
     const size_t lds = np_lds(A.S);
     for (uint32_t k = 0; k < n_epochs; k++) {
-        hipLaunchKernelGGL(k_plan_kinematics, dim3(1), dim3(NP_K1_THREADS), lds, (hipStream_t)stream, A, (const float*)states,
+        hipLaunchKernelGGL(k_plan_kinematics, dim3(K), dim3(NP_K1_THREADS), lds, (hipStream_t)stream, A, (const float*)states,
                            (const float*)initial_accel, body, (float*)nullptr, (float*)nullptr, points);
-        NGP_CHECK_LAUNCH("plan_epochs: kinematics");
+        { const hipError_t e = hipGetLastError(); if (e != hipSuccess) return ngp_fail(NGP_ELAUNCH, "%s: kinematics: %s", who, hipGetErrorString(e)); }
         const int rc_q = ngp_nav_density_value_jac(field, prepared, points, M, cfg->rot, sigma, jac, stream);
         if (rc_q != NGP_OK) return rc_q;
-        hipLaunchKernelGGL(k_plan_cost_step, dim3(1), dim3(NP_K3_THREADS), lds, (hipStream_t)stream, A, first_epoch + k, update, states,
-                           initial_accel, adam_state, body, (const float*)sigma, (const float*)jac, losses ? losses + k : (float*)nullptr,
-                           k + 1 == n_epochs ? per_state : (float*)nullptr);
-        NGP_CHECK_LAUNCH("plan_epochs: cost step");
+        hipLaunchKernelGGL(k_plan_cost_step, dim3(K), dim3(NP_K3_THREADS), lds, (hipStream_t)stream, A, first_epoch + k, update, states,
+                           initial_accel, adam_states, body, (const float*)sigma, (const float*)jac,
+                           losses ? losses + (size_t)k * K : (float*)nullptr, k + 1 == n_epochs ? per_state : (float*)nullptr);
+        { const hipError_t e = hipGetLastError(); if (e != hipSuccess) return ngp_fail(NGP_ELAUNCH, "%s: cost step: %s", who, hipGetErrorString(e)); }
     }
+    return NGP_OK;
+}
+
+extern "C" int ngp_plan_epochs(const ngp_nav_field_t* field, const void* prepared, const ngp_plan_cfg_t* cfg, float* states,
+                               float* initial_accel, float* adam_state, const float* body, uint32_t B, uint32_t R, uint32_t first_epoch,
+                               uint32_t n_epochs, int update, float* losses, float* per_state, void* workspace, size_t workspace_bytes,
+                               void* stream) {
+    np_args A;
+    const int rc = np_fill("plan_epochs", cfg, R, B, A);
+    if (rc != NGP_OK) return rc;
+    return np_epochs("plan_epochs", "ngp_plan_workspace(R, B)", A, field, prepared, cfg, 1, states, initial_accel, adam_state, body, first_epoch, n_epochs,
+                     update, losses, per_state, workspace, workspace_bytes, stream);
+}
+
+extern "C" int ngp_plan_epochs_multi(const ngp_nav_field_t* field, const void* prepared, const ngp_plan_cfg_t* cfg, uint32_t K, float* states,
+                                     float* initial_accel, float* adam_states, const float* body, uint32_t B, uint32_t R, uint32_t first_epoch,
+                                     uint32_t n_epochs, int update, float* losses, float* per_state, void* workspace, size_t workspace_bytes,
+                                     void* stream) {
+    NGP_REQUIRE(K >= 1 && K <= NGP_PLAN_MULTI_MAX_K, "plan_epochs_multi: K = %u hypotheses; supported 1 <= K <= %u", K, NGP_PLAN_MULTI_MAX_K);
+    np_args A;
+    const int rc = np_fill("plan_epochs_multi", cfg, R, B, A);
+    if (rc != NGP_OK) return rc;
+    NGP_REQUIRE((uint64_t)K * A.S * B <= NP_MAX_POINTS, "plan_epochs_multi: K * S * B = %u * %u * %u body points per epoch; supported K * S * B <= 2^26", K,
+                A.S, B);
+    return np_epochs("plan_epochs_multi", "ngp_plan_multi_workspace(K, R, B)", A, field, prepared, cfg, K, states, initial_accel, adam_states, body,
+                     first_epoch, n_epochs, update, losses, per_state, workspace, workspace_bytes, stream);
+}
+
+// one workgroup: every lane scans the K losses (K <= 64) by the rule of ngp_select.h, the lanes copy the winner's 4 R states and 2 accelerations, lane 0 its
+// loss and index
+static constexpr uint32_t NP_SELECT_THREADS = 256;
+__global__ __launch_bounds__(NP_SELECT_THREADS) void k_plan_select(const float* __restrict__ losses, const float* __restrict__ states,
+                                                                   const float* __restrict__ ia, uint32_t K, uint32_t R, float* __restrict__ best_states,
+                                                                   float* __restrict__ best_accel, float* __restrict__ best_loss,
+                                                                   uint32_t* __restrict__ best_index) {
+    const uint32_t best = ngp_select_best(losses, K);
+    const float* src = states + 4 * (size_t)R * best;
+    for (uint32_t e = threadIdx.x; e < 4 * R; e += blockDim.x) best_states[e] = src[e];
+    if (threadIdx.x < 2) best_accel[threadIdx.x] = ia[2 * (size_t)best + threadIdx.x];
+    if (threadIdx.x == 0) { *best_loss = losses[best]; *best_index = best; }
+}
+
+static int np_select_args(const char* who, const float* losses, const float* states, const float* initial_accel, uint32_t K, uint32_t R,
+                          float* best_states, float* best_accel, float* best_loss, uint32_t* best_index) {
+    NGP_REQUIRE(K >= 1 && K <= NGP_PLAN_MULTI_MAX_K, "%s: K = %u hypotheses; supported 1 <= K <= %u", who, K, NGP_PLAN_MULTI_MAX_K);
+    NGP_REQUIRE(R >= NP_MIN_R && R <= NP_MAX_R, "%s: R = %u rows of states; supported 2 <= R <= 255", who, R);
+    NGP_REQUIRE(losses && states && initial_accel && best_states && best_accel && best_loss && best_index, "%s: null pointer", who);
+    return NGP_OK;
+}
+
+extern "C" int ngp_plan_select(const float* losses, const float* states, const float* initial_accel, uint32_t K, uint32_t R, float* best_states,
+                               float* best_accel, float* best_loss, uint32_t* best_index, void* stream) {
+    const int rc = np_select_args("plan_select", losses, states, initial_accel, K, R, best_states, best_accel, best_loss, best_index);
+    if (rc != NGP_OK) return rc;
+    hipLaunchKernelGGL(k_plan_select, dim3(1), dim3(NP_SELECT_THREADS), 0, (hipStream_t)stream, losses, states, initial_accel, K, R, best_states, best_accel,
+                       best_loss, best_index);
+    NGP_CHECK_LAUNCH("plan_select");
+    return NGP_OK;
+}
+
+extern "C" int ngp_plan_select_host(const float* losses, const float* states, const float* initial_accel, uint32_t K, uint32_t R, float* best_states,
+                                    float* best_accel, float* best_loss, uint32_t* best_index) {
+    const int rc = np_select_args("plan_select_host", losses, states, initial_accel, K, R, best_states, best_accel, best_loss, best_index);
+    if (rc != NGP_OK) return rc;
+    const uint32_t best = ngp_select_best(losses, K);
+    for (uint32_t e = 0; e < 4 * R; e++) best_states[e] = states[4 * (size_t)R * best + e];
+    for (uint32_t e = 0; e < 2; e++) best_accel[e] = initial_accel[2 * (size_t)best + e];
+    *best_loss = losses[best];
+    *best_index = best;
     return NGP_OK;
 }

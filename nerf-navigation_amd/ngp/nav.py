@@ -665,13 +665,138 @@ class NativePlanner:
             head = tail
         return self.losses
 
-    def learn_init(self):
-        """Planner.learn_init: epochs_init epochs from fresh Adam moments"""
-        return self._learn(self.epochs_init, "init", lambda k: f"{k}.json")
+    def learn_init(self, offsets=None):
+        """Planner.learn_init: epochs_init epochs from fresh Adam moments.  offsets [K,R,4]: the multi-start route (`_learn_multi`); None: the single one"""
+        name = lambda k: f"{k}.json"                        # noqa: E731
+        return self._learn(self.epochs_init, "init", name) if offsets is None else self._learn_multi(self.epochs_init, "init", name, offsets)
 
-    def learn_update(self, iteration):
-        """Planner.learn_update: epochs_update epochs from fresh Adam moments"""
-        return self._learn(self.epochs_update, "replan", lambda k: f"{k}_time{iteration}.json")
+    def learn_update(self, iteration, offsets=None):
+        """Planner.learn_update: epochs_update epochs from fresh Adam moments.  offsets [K,R,4]: the multi-start route; None: the single one"""
+        name = lambda k: f"{k}_time{iteration}.json"        # noqa: E731
+        return self._learn(self.epochs_update, "replan", name) if offsets is None else self._learn_multi(self.epochs_update, "replan", name, offsets)
+
+    # -- multi-start: K trajectories of one objective in one launch sequence (DESIGN 3.5 "Multi-start planner") ------------------
+    def _workspace_multi(self, K):
+        import ngp_hip as _hip
+        B = int(self.robot_body.shape[0])
+        nbytes = _hip.lib().ngp_plan_multi_workspace(int(K), self.R, B)
+        if nbytes == 0:
+            raise ValueError(f"{K} hypotheses of {self.S} states and {B} body points: supported 1 <= K <= {_hip.PLAN_MULTI_MAX_K} and K * S * B <= 2^26")
+        if self._ws is None or self._ws.numel() < nbytes:
+            self._ws = _hip.workspace(nbytes, self.device)
+        return self._ws
+
+    def new_adam_state_multi(self, K):
+        """zeroed Adam moments and steps of K hypotheses: [K, plan_adam_floats(R)]"""
+        import ngp_hip as _hip
+        return torch.zeros(int(K), _hip.plan_adam_floats(self.R), dtype=torch.float32, device=self.device)
+
+    def run_epochs_multi(self, states, initial_accel, first_epoch, n_epochs, adam_states, update=True, losses=None, per_state=None):
+        """run_epochs for K hypotheses of the same objective (this planner's start, end, cfg and body): 3 launches per epoch whatever K is, no
+        synchronisation.  states: contiguous float32 [K,R,4] on the GPU (R = self.R), initial_accel [K,2], both updated in place; adam_states
+        [K, plan_adam_floats(R)] from new_adam_state_multi; losses [n_epochs,K], per_state [K,2,S] (of the last epoch): device tensors or None.  Row k of
+        every result is bit for bit run_epochs' from states[k], initial_accel[k]."""
+        import ctypes
+        import ngp_hip as _hip
+
+        def ok(t, shape):
+            return t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape
+        if not (torch.is_tensor(states) and states.dim() == 3 and states.shape[0] >= 1 and ok(states, (states.shape[0], self.R, 4))):
+            raise ValueError(f"states must be a contiguous float32 [K, {self.R}, 4] tensor on the GPU")
+        K = int(states.shape[0])
+        if not ok(initial_accel, (K, 2)):
+            raise ValueError(f"initial_accel must be a contiguous float32 [{K}, 2] tensor on the GPU")
+        if not ok(adam_states, (K, _hip.plan_adam_floats(self.R))):
+            raise ValueError(f"adam_states must be a contiguous float32 [{K}, {_hip.plan_adam_floats(self.R)}] tensor on the GPU (new_adam_state_multi)")
+        for name, t, shape in (("losses", losses, (int(n_epochs), K)), ("per_state", per_state, (K, 2, self.S))):
+            if t is not None and not ok(t, shape):
+                raise ValueError(f"{name} must be a contiguous float32 {list(shape)} tensor on the GPU")
+        st, prep = self.queries.native.struct()
+        ws = self._workspace_multi(K)
+        c = self._cfg_struct()
+        _hip.check(_hip.lib().ngp_plan_epochs_multi(ctypes.byref(st), _hip.ptr(prep), ctypes.byref(c), K, _hip.ptr(states), _hip.ptr(initial_accel),
+                                                    _hip.ptr(adam_states), _hip.ptr(self.robot_body), int(self.robot_body.shape[0]), self.R,
+                                                    int(first_epoch), int(n_epochs), 1 if update else 0, _hip.ptr(losses), _hip.ptr(per_state),
+                                                    _hip.ptr(ws), ws.numel(), _hip.stream()), "plan_epochs_multi")
+
+    def select(self, losses, states, initial_accel):
+        """ngp_plan_select: the hypothesis with the best loss, on the device -> (states [R,4], initial_accel [2], loss [1], index [1] int32).  The rule is
+        the pose filter's: indices are scanned in ascending order; a candidate replaces the best when its loss is smaller, or when the best is NaN and
+        the candidate is not: ties keep the lowest index, K NaNs give index 0.  One launch, no host read."""
+        import ngp_hip as _hip
+        losses, states, initial_accel = losses.contiguous(), states.contiguous(), initial_accel.contiguous()
+        K = int(losses.numel())
+        if not (all(t.is_cuda and t.dtype == torch.float32 for t in (losses, states, initial_accel)) and losses.dim() == 1 and states.dim() == 3
+                and tuple(states.shape) == (K, states.shape[1], 4) and tuple(initial_accel.shape) == (K, 2)):
+            raise ValueError("select takes float32 losses [K], states [K, R, 4] and initial_accel [K, 2] on the GPU")
+        R = int(states.shape[1])
+        best = torch.empty(R, 4, dtype=torch.float32, device=self.device)
+        accel = torch.empty(2, dtype=torch.float32, device=self.device)
+        loss = torch.empty(1, dtype=torch.float32, device=self.device)
+        index = torch.empty(1, dtype=torch.int32, device=self.device)           # the C side writes a uint32 <= 63
+        _hip.check(_hip.lib().ngp_plan_select(_hip.ptr(losses), _hip.ptr(states), _hip.ptr(initial_accel), K, R, _hip.ptr(best), _hip.ptr(accel),
+                                              _hip.ptr(loss), _hip.ptr(index), _hip.stream()), "plan_select")
+        return best, accel, loss, index
+
+    def draw_offsets(self, K, amplitude, generator=None):
+        """One choice of K starts for learn_init / learn_update (how starts are chosen stays the caller's business) -> offsets [K,R,4] on the device.
+        Row 0 is zero: hypothesis 0 is the single route's start.  Row k >= 1 bends the whole path sideways: amplitude * u_k * sin(pi (i + 1) / (R + 1))
+        on x, y, z of state i and 0 on the heading, u_k the unit vector of row k of torch.randn(K, 3, generator=generator), drawn on the CPU so that a
+        seed reproduces on any device."""
+        import math
+        K, R = int(K), self.R
+        if K < 1:
+            raise ValueError(f"draw_offsets: K = {K} hypotheses; at least 1")
+        u = torch.randn(K, 3, generator=generator)
+        u = u / u.norm(dim=1, keepdim=True)
+        bump = torch.sin(math.pi * (torch.arange(R, dtype=torch.float32) + 1) / (R + 1))
+        offsets = torch.zeros(K, R, 4, dtype=torch.float32)
+        offsets[1:, :, :3] = float(amplitude) * u[1:, None, :] * bump[None, :, None]
+        return offsets.to(self.device)
+
+    def _learn_multi(self, n, folder_tag, name, offsets):
+        """n epochs of K hypotheses, hypothesis k from self.states + offsets[k] with self.initial_accel and fresh Adam moments, in one call; then one more
+        pass with update = 0 at epoch index n - 1 (cost_and_gradient's default index after the run, so the fade-out mask agrees) gives every
+        hypothesis' final total_cost, and `select` picks the winner.  states / initial_accel become the winner's, epoch = n - 1, losses the winner's
+        column (gathered on the device with the index tensor: nothing is read to the host).  Keeps multi = dict(states [K,R,4], initial_accel [K,2],
+        final_losses [K], index [1] int32, losses [n,K]).  With `basefolder` set the reference's saves (it % 50 == 0) write the hypothesis that is best at
+        that epoch: one measurement pass and one select into scratch tensors, the hypotheses untouched."""
+        if n < 1:
+            raise ValueError("the multi-start route compares the hypotheses at the last epoch: at least 1 epoch is needed")
+        offsets = torch.as_tensor(offsets).detach().to(self.device, torch.float32)
+        if offsets.dim() != 3 or offsets.shape[0] < 1 or tuple(offsets.shape[1:]) != (self.R, 4):
+            raise ValueError(f"offsets must be [K, {self.R}, 4] (K hypotheses of this planner's R = {self.R} states), got {list(offsets.shape)}")
+        K = int(offsets.shape[0])
+        self._workspace_multi(K)                            # K out of range: ValueError before anything runs
+        kw = dict(dtype=torch.float32, device=self.device)
+        states = (self.states[None] + offsets).contiguous()
+        accel = self.initial_accel[None].repeat(K, 1).contiguous()
+        adam, scratch = self.new_adam_state_multi(K), self.new_adam_state_multi(K)
+        losses, final = torch.empty(n, K, **kw), torch.empty(1, K, **kw)
+
+        def best_at(epoch):                                 # the measurement pass: cost only, its gradient goes to the scratch moments' grad slot
+            self.run_epochs_multi(states, accel, epoch, 1, scratch, update=False, losses=final)
+            return self.select(final[0], states, accel)
+        base = getattr(self, "basefolder", None)
+        if base is None:
+            self.run_epochs_multi(states, accel, 0, n, adam, losses=losses)
+        else:
+            head = 0
+            while head < n:                                 # the single route's chunks: a save after the step of every epoch it % 50 == 0
+                tail = min(n, head + 1 if head == 0 else head + self.SAVE_STEP)
+                self.run_epochs_multi(states, accel, head, tail - head, adam, losses=losses[head:tail])
+                it = tail - 1
+                if it % self.SAVE_STEP == 0:
+                    self.states, self.initial_accel, _, _ = best_at(it)
+                    self.epoch = it
+                    self.save_poses(base / f"{folder_tag}_poses" / name(it // self.SAVE_STEP))
+                    self.save_costs(base / f"{folder_tag}_costs" / name(it // self.SAVE_STEP))
+                head = tail
+        self.states, self.initial_accel, _, index = best_at(n - 1)
+        self.epoch = n - 1
+        self.multi = dict(states=states, initial_accel=accel, final_losses=final[0], index=index, losses=losses)
+        self.losses = losses.index_select(1, index.long()).reshape(n)
+        return self.losses
 
     def update_state(self, measured_state):
         """Planner.update_state: the measured state becomes the start, states[0] is dropped, initial_accel = actions[1:3, 0]"""
@@ -1496,7 +1621,7 @@ SIMULATE_FOLDERS = ("init_poses", "init_costs", "replan_poses", "replan_costs", 
 
 
 def simulate(planner_cfg, agent_cfg, filter_cfg, extra_cfg, queries, sensor=None, basefolder=None, generator=None, interest_regions=None, seed=None,
-             filter_offsets=None):
+             filter_offsets=None, planner_starts=None):
     """simulate.simulate (simulate.py:18-102) over the native planner, agent and filter: A* and learn_init, then per MPC step the planner's action, the agent's
     noisy step and observation, the filter's time step and, before `steps - 5`, update_state and learn_update.
 
@@ -1506,6 +1631,8 @@ def simulate(planner_cfg, agent_cfg, filter_cfg, extra_cfg, queries, sensor=None
     (features="native", the draw keyed by `seed`) unless interest_regions ([M,2] (row, col)) are given, which are then used every step with
     numpy's default_rng(seed).  seed also seeds a_star_init's path noise; None leaves all three to the global / operating-system sources, as the reference.
     filter_offsets [K,12]: every time step of the filter is the multi-start one (estimate_state's `offsets`); None: the loop as it is.
+    planner_starts dict(K=..., amplitude=...): learn_init and every learn_update take the planner's multi-start route from draw_offsets(K, amplitude) at
+    the current R, drawn from a generator of their own (seeded by `seed`; the global one when seed is None); None: the loop as it is.
     basefolder: a directory (created when missing) that receives the reference's five sub-folders, init_* and replan_* from the planner, estimator_data/
     step{n}.json from the filter and true_states.json from the agent; None: nothing touches the disk.  Never prompts.
     -> dict(true_states [steps+1,12], estimates [steps,12], actions [steps,4], noises [steps,12] on the device; planner, agent, filter)."""
@@ -1521,7 +1648,11 @@ def simulate(planner_cfg, agent_cfg, filter_cfg, extra_cfg, queries, sensor=None
     if basefolder is not None:
         traj.basefolder = basefolder
     traj.a_star_init(generator=None if seed is None else torch.Generator().manual_seed(int(seed)), **planner_cfg.get("a_star", {}))
-    traj.learn_init()
+    starts_gen = None if seed is None else torch.Generator().manual_seed(int(seed))         # apart from the A* noise's: the default loop draws nothing more
+
+    def starts():
+        return None if planner_starts is None else traj.draw_offsets(planner_starts["K"], planner_starts["amplitude"], starts_gen)
+    traj.learn_init(offsets=starts())
     # 18-vector (rotation matrix) -> 12-vector (rotation vector)
     s18 = torch.as_tensor(start_state).detach().cpu().float()
     start12 = torch.cat([s18[:6], _rot_matrix_to_vec(s18[6:15].reshape(3, 3)), s18[15:]], dim=-1).to(traj.device)
@@ -1548,7 +1679,7 @@ def simulate(planner_cfg, agent_cfg, filter_cfg, extra_cfg, queries, sensor=None
         if row is None:
             # 12-vector -> 18-vector; the planner replans from the estimate
             traj.update_state(torch.cat([state_est[:6], _vec_to_rot_matrix(state_est[6:9]).reshape(-1), state_est[9:]], dim=-1))
-            traj.learn_update(it)
+            traj.learn_update(it, offsets=starts())
     if basefolder is not None:
         agent.save_data(basefolder / "true_states.json")
     return dict(true_states=agent.states_history.clone(), estimates=estimates, actions=actions, noises=noises, planner=traj, agent=agent, filter=filt)

@@ -140,6 +140,10 @@ _SIGNATURES = {
     "ngp_plan_workspace": (c_sz, [c_u32, c_u32]),
     "ngp_plan_kinematics": (c_int, [c_vp, c_vp, c_vp, c_u32, c_vp, c_u32, c_vp, c_vp, c_vp, c_vp]),
     "ngp_plan_epochs": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_u32, c_u32, c_u32, c_u32, c_int, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "ngp_plan_multi_workspace": (c_sz, [c_u32, c_u32, c_u32]),
+    "ngp_plan_epochs_multi": (c_int, [c_vp, c_vp, c_vp, c_u32, c_vp, c_vp, c_vp, c_vp, c_u32, c_u32, c_u32, c_u32, c_int, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "ngp_plan_select": (c_int, [c_vp, c_vp, c_vp, c_u32, c_u32, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "ngp_plan_select_host": (c_int, [c_vp, c_vp, c_vp, c_u32, c_u32, c_vp, c_vp, c_vp, c_vp]),
     "ngp_plan_occupancy": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_u32, c_u32, c_vp, c_f32, c_vp, c_vp]),
     "ngp_plan_astar": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_u32, c_vp, c_vp]),
     "ngp_plan_astar_host": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_u32, c_vp]),
@@ -228,6 +232,7 @@ class ngp_features_cfg_t(ctypes.Structure):
 
 FILTER_ADAM_FLOATS = 37                                      # include/ngp_hip.h: NGP_FILTER_ADAM_FLOATS
 FILTER_MULTI_MAX_K = 64                                      # include/ngp_hip.h: NGP_FILTER_MULTI_MAX_K
+PLAN_MULTI_MAX_K = 64                                        # include/ngp_hip.h: NGP_PLAN_MULTI_MAX_K
 
 
 def build(verbose=False):
