@@ -548,6 +548,35 @@ int ngp_nav_run_backward(const ngp_nav_field_t* field_host, const void* prepared
                          const float* grad_image, const float* grad_depth, const float* grad_weights_sum, const void* saved, size_t saved_bytes,
                          float* grad_rays_o, float* grad_rays_d, void* stream);
 
+/* The same run with the occupancy grid consulted (DESIGN.md 3.5 "Occupancy-masked pose filter"): the sigma of every lattice sample whose occupancy
+ * bit is clear is zero; everything else (nears, fars, the lattice, the clipped positions, the deltas of the lattice, the colour mask, depth, the
+ * background mix) is ngp_nav_run_forward's.  The bit of a sample is that of its clipped float32 position x under the march's cell arithmetic with the
+ * step's cascade left out: level = clamp(frexp exponent of max(|x|,|y|,|z|), 0, C - 1), mip_bound = min(2^level, bound),
+ * n = (int)clamp(((x * (1 / mip_bound) + 1) * 0.5) * Hgrid, 0, Hgrid - 1) per axis, bit = level * Hgrid^3 + morton3(nx, ny, nz).  The mask is a constant:
+ * grad_rays_o, grad_rays_d are the masked function's exact derivatives.  One wave per ray; the field is evaluated at the occupied samples only; a ray
+ * without one gets the background, zero depth, zero weights_sum and zero gradients.  No atomics: two runs give the same bits, and a ray's outputs do not
+ * depend on the other rays of the launch. */
+typedef struct {
+    const uint8_t* bitfield;     /* device, C * Hgrid^3 / 8 bytes: NeRFRenderer.density_bitfield */
+    uint32_t C;                  /* cascades, >= 1 */
+    uint32_t Hgrid;              /* grid size per axis: a power of two in [2, 1024], C * Hgrid^3 <= 2^32 */
+} ngp_occ_grid_t;
+/* bytes the forward keeps for the backward: ngp_nav_run_saved_bytes(N, num_steps) (every sample occupied) + counts [N] u32 + lists [N, num_steps] u16,
+ * rounded up to 256; nothing needs clearing.  0 for N = 0 or num_steps = 0. */
+size_t ngp_nav_run_occ_saved_bytes(uint32_t N, uint32_t num_steps);
+/* The arguments of ngp_nav_run_forward plus grid_host and counts [N] u32 (may be NULL): the occupied samples of each ray.  Refused with NGP_EINVAL on
+ * the host before anything is queued: a null grid or bitfield, C = 0, an Hgrid that is not a power of two, num_steps outside [1, 4096], a short `saved`. */
+int ngp_nav_run_occ_forward(const ngp_nav_field_t* field_host, const void* prepared, const ngp_occ_grid_t* grid_host, const float* rays_o,
+                            const float* rays_d, const float* nears, const float* fars, uint32_t N, uint32_t num_steps, const float* aabb_host,
+                            const float* bg_color3_host, float* image, float* depth, float* weights_sum, uint32_t* counts, void* saved,
+                            size_t saved_bytes, void* stream);
+/* The arguments of ngp_nav_run_backward plus grid_host; `saved` is what ngp_nav_run_occ_forward filled for the same rays (the samples walked are the
+ * forward's own lists). */
+int ngp_nav_run_occ_backward(const ngp_nav_field_t* field_host, const void* prepared, const ngp_occ_grid_t* grid_host, const float* rays_o,
+                             const float* rays_d, const float* nears, const float* fars, uint32_t N, uint32_t num_steps, const float* aabb_host,
+                             const float* bg_color3_host, const float* grad_image, const float* grad_depth, const float* grad_weights_sum,
+                             const void* saved, size_t saved_bytes, float* grad_rays_o, float* grad_rays_d, void* stream);
+
 /* Training forward and backward of the same field (NeRFNetwork.forward, nerf/network.py:95-123, float32; csrc/nav_train.hip).
  * forward: xyzs, dirs [M,3] -> sigmas [M] = exp(h0) (field_host->density_scale is NOT applied: the renderer does that), rgbs [M,3] after the sigmoid;
  *   a sample outside [-bound, bound]^3 encodes to zeros.  saved: ngp_nav_field_train_saved_bytes(M) bytes (the 32 encoded features, 128 B per sample).
@@ -813,6 +842,23 @@ int ngp_filter_propagate(const ngp_filter_dyn_t* dyn_host, const float* state, c
 int ngp_filter_hessian(const ngp_nav_field_t* field_host, const void* prepared, const ngp_filter_cfg_t* cfg_host, const float* state,
                        const float* target, const int32_t* batch, float* hessian, float* grad, float* loss, float* dLdP,
                        void* workspace, size_t workspace_bytes, void* stream);
+
+/* The loop and the Hessian over the occupancy-masked run (ngp_nav_run_occ_forward / _backward in the measurement pass; DESIGN.md 3.5 "Occupancy-masked
+ * pose filter"): opt-in, the entry points above keep their code path.  grid_host as for ngp_nav_run_occ_forward; a null grid is refused with NGP_EINVAL.
+ * bytes of their workspace: the pieces of ngp_filter_multi_workspace(K, B, num_steps) with ngp_nav_run_occ_saved_bytes(K B, num_steps) as the record;
+ * 0 outside the shapes ngp_filter_multi_workspace supports. */
+size_t ngp_filter_occ_workspace(uint32_t K, uint32_t B, uint32_t num_steps);
+/* ngp_filter_iterations_multi's arguments plus the grid: K >= 1 hypotheses (K = 1: the single loop, states [1,12], losses [n_iter,1]); row k of every
+ * output is bit for bit the K = 1 run from states[k].  workspace: ngp_filter_occ_workspace(K, B, num_steps) bytes, NGP_EWORKSPACE below that. */
+int ngp_filter_iterations_occ(const ngp_nav_field_t* field_host, const void* prepared, const ngp_filter_cfg_t* cfg_host, const ngp_occ_grid_t* grid_host,
+                              uint32_t K, float* states, float* adam_states, const float* target, const int32_t* batches, uint32_t first_iter,
+                              uint32_t n_iter, int update, float* losses, float* states_out, float* grads_out, void* workspace,
+                              size_t workspace_bytes, void* stream);
+/* ngp_filter_hessian's arguments plus the grid; gradient and loss are bit for bit what an update = 0 iteration of ngp_filter_iterations_occ writes.
+ * workspace: ngp_filter_occ_workspace(1, B, num_steps) bytes. */
+int ngp_filter_hessian_occ(const ngp_nav_field_t* field_host, const void* prepared, const ngp_filter_cfg_t* cfg_host, const ngp_occ_grid_t* grid_host,
+                           const float* state, const float* target, const int32_t* batch, float* hessian, float* grad, float* loss, float* dLdP,
+                           void* workspace, size_t workspace_bytes, void* stream);
 
 /* The front of the time step: the sensor image's interest regions and the loop's batches (Estimator.find_POI, the dilation, coords[mask] and the draw,
  * nav/estimator_helpers.py:181-204, 229-230; csrc/nav_features.hip, csrc/ngp_features.h, DESIGN.md §3.5 "Native interest regions").

@@ -15,12 +15,15 @@
 //                              image / depth / weights_sum reductions; the backward recomputes the forward, derives d L / d sigma_i
 //                              analytically (prefix product + suffix sum), and runs colour-net and density-net backward per sample down
 //                              to d L / d xyz, reduced into d L / d rays_o and d L / d rays_d.
+//   k_nav_run_occ_fwd / _bwd   the same run with the occupancy grid consulted (sigma = 0 where the bit is clear), one WAVE per ray over the compacted
+//                              list of its occupied samples: the pose filter's opt-in route (the section before "host side" below)
 // float32 FMA throughput is the same on the VALU and on the f32 MFMA of this chip, and the batch is small (10 k - 524 k points), so
 // the matrix cores would buy nothing here; what the fusion removes is launches and the [M, 64] round trips through HBM.
 //
 // Arithmetic: float32 like the reference path, but sums are fused multiply-adds in a fixed order of their own (rocBLAS has its own):
 // results agree with the torch path to float32 rounding (tests/test_gpu_nav_native.py states the tolerances against the CPU oracle).
 #include "ngp_nav_field.h"
+#include "ngp_march.h"                                                       // ngp_point::at: the cell of a position (the occupancy-masked run)
 
 // ---------------------------------------------------------------------------
 // density queries on explicit points (planner: nav/quad_plot.py:224-250)
@@ -344,6 +347,7 @@ __global__ __launch_bounds__(NV_BLOCK) void k_nav_run_fwd(nav_params P, nav_run 
 }
 
 // colour net backward from the saved forward: grgb[3] = d L / d rgb  ->  ggeo[15], d L / d dir (added)
+template <uint32_t S = NV_BLOCK>
 __device__ __forceinline__ void nv_color_backward_saved(const nav_params& P, float dxr, float dyr, float dzr, const float (&rgb)[3], uint64_t mask_a,
                                                         uint64_t mask_b, const float (&grgb)[3], float* __restrict__ col, float (&ggeo)[NV_GEO],
                                                         float& gdx, float& gdy, float& gdz) {
@@ -351,15 +355,15 @@ __device__ __forceinline__ void nv_color_backward_saved(const nav_params& P, flo
     #pragma unroll
     for (int c = 0; c < 3; c++) go[c] = grgb[c] * rgb[c] * (1.0f - rgb[c]);
     float g[NV_H];
-    nv_park(go, col);
-    nv_matvec<3, NV_H>(P.v2, col, g);                                    // d L / d hb
+    nv_park<S>(go, col);
+    nv_matvec<3, NV_H, S>(P.v2, col, g);                                 // d L / d hb
     #pragma unroll
-    for (int j = 0; j < NV_H; j++) col[j * NV_BLOCK] = ((mask_b >> j) & 1ull) ? g[j] : 0.0f;
-    nv_matvec<NV_H, NV_H>(P.v1, col, g);                                 // d L / d ha
+    for (int j = 0; j < NV_H; j++) col[j * S] = ((mask_b >> j) & 1ull) ? g[j] : 0.0f;
+    nv_matvec<NV_H, NV_H, S>(P.v1, col, g);                              // d L / d ha
     #pragma unroll
-    for (int k = 0; k < NV_H; k++) col[k * NV_BLOCK] = ((mask_a >> k) & 1ull) ? g[k] : 0.0f;
+    for (int k = 0; k < NV_H; k++) col[k * S] = ((mask_a >> k) & 1ull) ? g[k] : 0.0f;
     float gin[NV_CIN];
-    nv_matvec<NV_H, NV_CIN>(P.v0, col, gin);                             // d L / d cat(SH, geo)
+    nv_matvec<NV_H, NV_CIN, S>(P.v0, col, gin);                            // d L / d cat(SH, geo)
     float gsh[16];
     #pragma unroll
     for (int i = 0; i < 16; i++) gsh[i] = gin[i];
@@ -450,6 +454,215 @@ __global__ __launch_bounds__(NV_BLOCK) void k_nav_run_bwd(nav_params P, nav_run 
     const float a0 = nv_block_sum(go0, lds4), a1 = nv_block_sum(go1, lds4), a2 = nv_block_sum(go2, lds4);
     const float b0 = nv_block_sum(gdx, lds4), b1 = nv_block_sum(gdy, lds4), b2 = nv_block_sum(gdz, lds4);
     if (threadIdx.x == 0) {
+        grays_o[3ull * n] = a0; grays_o[3ull * n + 1] = a1; grays_o[3ull * n + 2] = a2;
+        grays_d[3ull * n] = b0; grays_d[3ull * n + 1] = b1; grays_d[3ull * n + 2] = b2;
+    }
+}
+
+// ---------------------------------------------------------------------------
+// The same run with the occupancy grid consulted (DESIGN.md §3.5 "Occupancy-masked pose filter"): the sigma of every lattice sample whose occupancy bit
+// is clear is zero.  Such a sample has alpha = 0 and keep = 1 - 0 + 1e-15f = 1.0f exactly, so it drops out of every sum and of the transmittance product
+// without a rounding, and the kernels below never evaluate the field there: per ray they walk the T lattice positions (one bitfield byte each), compact
+// the indices of the occupied ones in lattice order, and run k_nav_run_fwd / _bwd's per-sample code over that list only.  Everything else is the dense
+// run's: nears, fars, nv_lin, the clipped positions, the deltas of the LATTICE (not merged over the gaps), the colour mask, depth and background.
+//
+// The bit of a sample is that of its clipped float32 position under the march's own cell arithmetic, ngp_point::at (ngp_march.h), through a view whose
+// "ray" is the position itself (origin = position, direction 0, parameter 0) and whose step is 0, which leaves the step's cascade out: level = mip of
+// the position alone.  The mask is a constant of the float32 position: no gradient flows through it.
+//
+// Shape: ONE WAVE PER RAY (workgroup = 64 lanes).  With ~45 live samples per ray three of k_nav_run_*'s four waves would idle; here the activation
+// scratch is [64][64] floats = 16 KB plus the list (T x 2 B <= 8 KB), the scans are shuffles only, and the single barrier (list written, list read)
+// is a wave barrier.  The helpers of ngp_nav_field.h take the column stride as a template parameter for this (S = 64).
+// No atomics; a ray's outputs depend on nothing but the ray; two runs give the same bits.
+// ---------------------------------------------------------------------------
+static constexpr uint32_t NO_W = 64;                                     // lanes per ray = the chunk width of the compacted list
+
+struct nav_occ { const uint8_t* bits; uint32_t H3; int Cm1; float rbound, hHf, Hm1; };
+
+struct nro_view {                                                        // what ngp_point<V>::at reads (ngp_march.h)
+    static constexpr bool pow2_grid = true;
+    float ox, oy, oz, dx, dy, dz, bound, rbound, dt_gamma, dt_min, dt_max, hHf, Hm1;
+    int Cm1;
+    __device__ __forceinline__ int mip(int e) const { return e < 0 ? 0 : (e > Cm1 ? Cm1 : e); }
+};
+
+__device__ __forceinline__ bool nro_occupied(const nav_occ& G, float bound, float px, float py, float pz) {
+    nro_view m;
+    m.ox = px; m.oy = py; m.oz = pz; m.dx = 0.0f; m.dy = 0.0f; m.dz = 0.0f;
+    m.bound = bound; m.rbound = G.rbound; m.dt_gamma = 0.0f; m.dt_min = 0.0f; m.dt_max = 0.0f;      // step 0: frexp exponent 0, cascade 0
+    m.hHf = G.hHf; m.Hm1 = G.Hm1; m.Cm1 = G.Cm1;
+    ngp_point<nro_view> p;
+    p.at(m, 0.0f);
+    const uint32_t bit = (uint32_t)p.level * G.H3 + ngp_morton3((uint32_t)p.nx, (uint32_t)p.ny, (uint32_t)p.nz);   // < C H^3 <= 2^32 (host check)
+    return (G.bits[bit >> 3] >> (bit & 7u)) & 1u;
+}
+
+__device__ __forceinline__ float nro_wave_sum(float v) {                // nv_block_sum's wave part; lane 0 holds the sum
+    #pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    return v;
+}
+
+// what the forward leaves besides the records: the ray's count and its list, so that the backward walks the same samples.  Record j of ray n (the j-th
+// occupied sample) sits where the dense run keeps sample j: word-major at n T + j
+struct nro_kept { uint32_t* save; uint32_t* counts; uint16_t* lists; };
+
+__global__ __launch_bounds__(NO_W) void k_nav_run_occ_fwd(nav_params P, nav_run R, nav_occ G, float* __restrict__ image, float* __restrict__ depth,
+                                                          float* __restrict__ weights_sum, uint32_t* __restrict__ counts_out, nro_kept K) {
+    extern __shared__ float nv_smem[];
+    const uint32_t lane = threadIdx.x;
+    float* col = nv_smem + lane;                                         // this lane's column of the [64][64] scratch
+    uint16_t* list = reinterpret_cast<uint16_t*>(nv_smem + NV_H * NO_W); // [T]
+    const uint32_t n = blockIdx.x;
+    const size_t NT = (size_t)R.N * R.T;
+    const float ox = R.rays_o[3ull * n], oy = R.rays_o[3ull * n + 1], oz = R.rays_o[3ull * n + 2];
+    const float dx = R.rays_d[3ull * n], dy = R.rays_d[3ull * n + 1], dz = R.rays_d[3ull * n + 2];
+    const float near = R.nears[n], far = R.fars[n], span = far - near;
+
+    // ---- the lattice walk: position and one bitfield byte per sample; the occupied indices, in lattice order, by ballot and prefix count ----
+    uint32_t count = 0;
+    for (uint32_t c0 = 0; c0 < R.T; c0 += NO_W) {
+        const uint32_t i = c0 + lane;
+        const bool live = i < R.T;
+        const nv_sample s = nv_sample_at(R, live ? i : R.T - 1, near, far, ox, oy, oz, dx, dy, dz);
+        const bool occ = live && nro_occupied(G, P.bound, s.px, s.py, s.pz);
+        const unsigned long long m = __ballot(occ);
+        if (occ) list[count + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = (uint16_t)i;       // < count + popc(m) <= T
+        count += (uint32_t)__popcll(m);                                  // wave-uniform
+    }
+    __syncthreads();                                                     // one wave: the list is written before it is read
+
+    float carry = 1.0f, acc_w = 0.0f, acc_d = 0.0f, acc_r = 0.0f, acc_g = 0.0f, acc_b = 0.0f;
+    for (uint32_t j0 = 0; j0 < count; j0 += NO_W) {
+        const uint32_t j = j0 + lane;
+        const bool live = j < count;
+        const uint32_t i = list[live ? j : count - 1];
+        const nv_sample s = nv_sample_at(R, i, near, far, ox, oy, oz, dx, dy, dz);
+        float x0, x1, x2;
+        const bool inside = nv_normalise(P, s.px, s.py, s.pz, x0, x1, x2);
+        float out[16];
+        const uint64_t relu = nv_density_forward<NV_RUN_U, NO_W>(P, inside, x0, x1, x2, col, out);
+        float ex, alpha, keep;
+        nv_alpha(s.znext_minus_z, P.density_scale, expf(out[0]), ex, alpha, keep);
+        if (!live) { alpha = 0.0f; keep = 1.0f; }
+        float incl = keep;                                               // exclusive product over the wave, nv_block_excl_product's wave part
+        #pragma unroll
+        for (int off = 1; off < 64; off <<= 1) { const float up = __shfl_up(incl, off, 64); if ((int)lane >= off) incl = up * incl; }
+        float before = __shfl_up(incl, 1, 64);
+        if (lane == 0) before = 1.0f;
+        const float total = __shfl(incl, 63, 64);
+        const float Tr = carry * before;
+        const float w = alpha * Tr;
+        uint32_t* q = K.save + (size_t)n * R.T + j;
+        if (K.save && live) {
+            K.lists[(size_t)n * R.T + j] = (uint16_t)i;
+            #pragma unroll
+            for (int m = 0; m < 16; m++) q[(NV_R_OUT + m) * NT] = __float_as_uint(out[m]);
+            q[NV_R_RELU * NT] = (uint32_t)relu; q[(NV_R_RELU + 1) * NT] = (uint32_t)(relu >> 32);
+            q[NV_R_EX * NT] = __float_as_uint(ex); q[NV_R_TR * NT] = __float_as_uint(Tr);
+        }
+        float rgb[3] = {0.0f, 0.0f, 0.0f};
+        uint64_t ma = 0, mb = 0;
+        if (live && w > 1e-4f) {
+            float geo[NV_GEO];
+            #pragma unroll
+            for (int m = 0; m < NV_GEO; m++) geo[m] = out[1 + m];
+            nv_color_forward<NO_W>(P, dx, dy, dz, geo, col, rgb, ma, mb);
+        }
+        if (K.save && live) {
+            q[NV_R_RGB * NT] = __float_as_uint(rgb[0]); q[(NV_R_RGB + 1) * NT] = __float_as_uint(rgb[1]); q[(NV_R_RGB + 2) * NT] = __float_as_uint(rgb[2]);
+            q[NV_R_MA * NT] = (uint32_t)ma; q[(NV_R_MA + 1) * NT] = (uint32_t)(ma >> 32);
+            q[NV_R_MB * NT] = (uint32_t)mb; q[(NV_R_MB + 1) * NT] = (uint32_t)(mb >> 32);
+        }
+        const float oz01 = fminf(fmaxf((s.z - near) / span, 0.0f), 1.0f);
+        acc_w += w; acc_d += w * oz01; acc_r += w * rgb[0]; acc_g += w * rgb[1]; acc_b += w * rgb[2];
+        carry *= total;
+    }
+    const float ws = nro_wave_sum(acc_w), dsum = nro_wave_sum(acc_d);
+    const float r = nro_wave_sum(acc_r), g = nro_wave_sum(acc_g), b = nro_wave_sum(acc_b);
+    if (lane == 0) {                                                     // an empty ray: ws = 0, so the image is bg bit for bit
+        weights_sum[n] = ws;
+        depth[n] = dsum;
+        image[3ull * n] = r + (1.0f - ws) * R.bg[0];
+        image[3ull * n + 1] = g + (1.0f - ws) * R.bg[1];
+        image[3ull * n + 2] = b + (1.0f - ws) * R.bg[2];
+        if (K.save) K.counts[n] = count;
+        if (counts_out) counts_out[n] = count;
+    }
+}
+
+__global__ __launch_bounds__(NO_W) void k_nav_run_occ_bwd(nav_params P, nav_run R, const float* __restrict__ gimage, const float* __restrict__ gdepth,
+                                                          const float* __restrict__ gws, nro_kept K, float* __restrict__ grays_o,
+                                                          float* __restrict__ grays_d) {
+    extern __shared__ float nv_smem[];
+    const uint32_t lane = threadIdx.x;
+    float* col = nv_smem + lane;
+    const uint32_t n = blockIdx.x;
+    const size_t NT = (size_t)R.N * R.T;
+    const float ox = R.rays_o[3ull * n], oy = R.rays_o[3ull * n + 1], oz = R.rays_o[3ull * n + 2];
+    const float dx = R.rays_d[3ull * n], dy = R.rays_d[3ull * n + 1], dz = R.rays_d[3ull * n + 2];
+    const float near = R.nears[n], far = R.fars[n], span = far - near;
+    const float gi0 = gimage[3ull * n], gi1 = gimage[3ull * n + 1], gi2 = gimage[3ull * n + 2];
+    const float gd = gdepth ? gdepth[n] : 0.0f, gw = gws ? gws[n] : 0.0f;
+    const uint32_t stored = K.counts[n];
+    const uint32_t count = stored < R.T ? stored : R.T;                  // the forward's own number; the clamp keeps a foreign buffer inside the ray's slice
+    const uint32_t nchunks = (count + NO_W - 1) / NO_W;
+    const uint16_t* list = K.lists + (size_t)n * R.T;
+
+    float suffix = 0.0f;                                                 // back to front, as k_nav_run_bwd: the sum over the samples behind
+    float go0 = 0.0f, go1 = 0.0f, go2 = 0.0f, gdx = 0.0f, gdy = 0.0f, gdz = 0.0f;
+    for (uint32_t cc = nchunks; cc-- > 0;) {
+        const uint32_t j = cc * NO_W + lane;
+        const bool live = j < count;
+        const uint32_t jc = live ? j : count - 1;
+        const uint32_t listed = list[jc];
+        const uint32_t i = listed < R.T ? listed : R.T - 1;
+        const nv_sample s = nv_sample_at(R, i, near, far, ox, oy, oz, dx, dy, dz);
+        const uint32_t* q = K.save + (size_t)n * R.T + jc;
+        const float ex = live ? __uint_as_float(q[NV_R_EX * NT]) : 1.0f, Tr = live ? __uint_as_float(q[NV_R_TR * NT]) : 0.0f;
+        const float alpha = 1.0f - ex;
+        const float rgb[3] = {__uint_as_float(q[NV_R_RGB * NT]), __uint_as_float(q[(NV_R_RGB + 1) * NT]), __uint_as_float(q[(NV_R_RGB + 2) * NT])};
+        const float w = alpha * Tr;
+        const bool masked = live && w > 1e-4f;
+        const float oz01 = fminf(fmaxf((s.z - near) / span, 0.0f), 1.0f);
+        const float A = live ? (gi0 * (rgb[0] - R.bg[0]) + gi1 * (rgb[1] - R.bg[1]) + gi2 * (rgb[2] - R.bg[2]) + gd * oz01 + gw) : 0.0f;
+        const float Aw = A * w;
+        float rs = __shfl_down(Aw, 1, 64);                               // exclusive by construction (k_nav_run_bwd says why)
+        if (lane == 63) rs = 0.0f;
+        #pragma unroll
+        for (int off = 1; off < 64; off <<= 1) { const float dn = __shfl_down(rs, off, 64); if (lane + off < 64) rs += dn; }
+        const float chunk_total = __shfl(rs + Aw, 0, 64);
+        const float S = suffix + rs;                                     // sum over the occupied k > i of A_k w_k; the others' w is zero
+        suffix += chunk_total;
+        const float keep = 1.0f - alpha + 1e-15f;
+        const float gsigma = live ? s.znext_minus_z * P.density_scale * ex * (A * Tr - S / keep) : 0.0f;
+
+        float gout[16];
+        #pragma unroll
+        for (int m = 0; m < 16; m++) gout[m] = 0.0f;
+        if (masked) {
+            float ggeo[NV_GEO];
+            const uint64_t ma = (uint64_t)q[NV_R_MA * NT] | ((uint64_t)q[(NV_R_MA + 1) * NT] << 32);
+            const uint64_t mb = (uint64_t)q[NV_R_MB * NT] | ((uint64_t)q[(NV_R_MB + 1) * NT] << 32);
+            const float grgb[3] = {gi0 * w, gi1 * w, gi2 * w};
+            nv_color_backward_saved<NO_W>(P, dx, dy, dz, rgb, ma, mb, grgb, col, ggeo, gdx, gdy, gdz);
+            #pragma unroll
+            for (int m = 0; m < NV_GEO; m++) gout[1 + m] = ggeo[m];
+        }
+        gout[0] = gsigma * nv_exp_clamped(__uint_as_float(q[NV_R_OUT * NT]));
+        const uint64_t relu = (uint64_t)q[NV_R_RELU * NT] | ((uint64_t)q[(NV_R_RELU + 1) * NT] << 32);
+        float x0, x1, x2;
+        const bool inside = nv_normalise(P, s.px, s.py, s.pz, x0, x1, x2);
+        float gx, gy, gz;
+        nv_density_backward<NV_RUN_U, NO_W>(P, inside, x0, x1, x2, relu, gout, col, gx, gy, gz);
+        if (!live) { gx = 0.0f; gy = 0.0f; gz = 0.0f; }
+        gx *= s.bx; gy *= s.by; gz *= s.bz;
+        go0 += gx; go1 += gy; go2 += gz;
+        gdx = __builtin_fmaf(s.z, gx, gdx); gdy = __builtin_fmaf(s.z, gy, gdy); gdz = __builtin_fmaf(s.z, gz, gdz);
+    }
+    const float a0 = nro_wave_sum(go0), a1 = nro_wave_sum(go1), a2 = nro_wave_sum(go2);
+    const float b0 = nro_wave_sum(gdx), b1 = nro_wave_sum(gdy), b2 = nro_wave_sum(gdz);
+    if (lane == 0) {                                                     // an empty ray: exact zeros
         grays_o[3ull * n] = a0; grays_o[3ull * n + 1] = a1; grays_o[3ull * n + 2] = a2;
         grays_d[3ull * n] = b0; grays_d[3ull * n + 1] = b1; grays_d[3ull * n + 2] = b2;
     }
@@ -588,5 +801,81 @@ extern "C" int ngp_nav_run_backward(const ngp_nav_field_t* f, const void* prepar
     hipLaunchKernelGGL(k_nav_run_bwd, dim3(N), dim3(NV_BLOCK), lds, (hipStream_t)stream, P, R, grad_image, grad_depth, grad_weights_sum,
                        (const uint32_t*)kept.p, grad_rays_o, grad_rays_d);
     NGP_CHECK_LAUNCH("nav_run_backward");
+    return NGP_OK;
+}
+
+// ---- the occupancy-masked run ----
+
+// records as the dense run keeps them (worst case: every sample occupied), then the counts [N] and the lists [N][T]; nothing needs clearing
+static nro_kept nro_layout(uint32_t N, uint32_t num_steps, void* base, size_t* total) {
+    const size_t nt = (size_t)N * num_steps;
+    ngp_carver c(base);
+    const nro_kept k = {c.take<uint32_t>(NV_REC_WORDS * nt, 1), c.take<uint32_t>(N), c.take<uint16_t>(nt)};
+    *total = nt ? c.total(256) : 0;
+    return k;
+}
+extern "C" size_t ngp_nav_run_occ_saved_bytes(uint32_t N, uint32_t num_steps) {
+    size_t total;
+    nro_layout(N, num_steps, nullptr, &total);
+    return total;
+}
+
+// Hgrid a power of two (the one-multiply cell coordinate, ngp_cell_coord), at most 1024 (ngp_morton3's 10 bits per axis), C H^3 bits indexed in 32 bits
+static int nro_grid(const char* who, const ngp_occ_grid_t* g, float bound, nav_occ& G) {
+    NGP_REQUIRE(g && g->bitfield, "%s: null occupancy grid", who);
+    NGP_REQUIRE(g->C >= 1 && g->C <= 32, "%s: C = %u cascades; supported 1 <= C <= 32", who, g->C);
+    NGP_REQUIRE(g->Hgrid >= 2 && g->Hgrid <= 1024 && (g->Hgrid & (g->Hgrid - 1u)) == 0u, "%s: Hgrid = %u; the grid size must be a power of two in [2, 1024]", who, g->Hgrid);
+    const uint64_t h3 = (uint64_t)g->Hgrid * g->Hgrid * g->Hgrid;
+    NGP_REQUIRE(h3 * g->C <= (1ull << 32), "%s: C * Hgrid^3 = %u * %u^3 bits do not fit a 32-bit index", who, g->C, g->Hgrid);
+    G.bits = g->bitfield; G.H3 = (uint32_t)h3; G.Cm1 = (int)g->C - 1;
+    G.rbound = 1.0f / bound; G.hHf = 0.5f * (float)g->Hgrid; G.Hm1 = (float)(g->Hgrid - 1u);
+    return NGP_OK;
+}
+
+extern "C" int ngp_nav_run_occ_forward(const ngp_nav_field_t* f, const void* prepared, const ngp_occ_grid_t* grid_host, const float* rays_o,
+                                       const float* rays_d, const float* nears, const float* fars, uint32_t N, uint32_t num_steps, const float* aabb_host,
+                                       const float* bg_color3_host, float* image, float* depth, float* weights_sum, uint32_t* counts, void* saved,
+                                       size_t saved_bytes, void* stream) {
+    nav_params P;
+    int rc = nav_fill("nav_run_occ_forward", f, prepared, P);
+    if (rc != NGP_OK) return rc;
+    nav_occ G;
+    rc = nro_grid("nav_run_occ_forward", grid_host, P.bound, G);
+    if (rc != NGP_OK) return rc;
+    if (N == 0) return NGP_OK;
+    nav_run R;
+    rc = nav_run_args("nav_run_occ_forward", rays_o, rays_d, nears, fars, N, num_steps, aabb_host, bg_color3_host, R);
+    if (rc != NGP_OK) return rc;
+    NGP_REQUIRE(image && depth && weights_sum, "nav_run_occ_forward: null output");
+    size_t total;
+    const nro_kept kept = nro_layout(N, num_steps, saved, &total);
+    NGP_REQUIRE(!saved || saved_bytes >= total, "nav_run_occ_forward: `saved` is smaller than ngp_nav_run_occ_saved_bytes(N, num_steps)");
+    const size_t lds = sizeof(float) * NV_H * NO_W + ((sizeof(uint16_t) * num_steps + 3) & ~(size_t)3);          // 16 KB + the list: below the default limit
+    hipLaunchKernelGGL(k_nav_run_occ_fwd, dim3(N), dim3(NO_W), lds, (hipStream_t)stream, P, R, G, image, depth, weights_sum, counts, kept);
+    NGP_CHECK_LAUNCH("nav_run_occ_forward");
+    return NGP_OK;
+}
+
+extern "C" int ngp_nav_run_occ_backward(const ngp_nav_field_t* f, const void* prepared, const ngp_occ_grid_t* grid_host, const float* rays_o,
+                                        const float* rays_d, const float* nears, const float* fars, uint32_t N, uint32_t num_steps, const float* aabb_host,
+                                        const float* bg_color3_host, const float* grad_image, const float* grad_depth, const float* grad_weights_sum,
+                                        const void* saved, size_t saved_bytes, float* grad_rays_o, float* grad_rays_d, void* stream) {
+    nav_params P;
+    int rc = nav_fill("nav_run_occ_backward", f, prepared, P);
+    if (rc != NGP_OK) return rc;
+    nav_occ G;                                                           // the samples come from the forward's lists; the grid is only judged here
+    rc = nro_grid("nav_run_occ_backward", grid_host, P.bound, G);
+    if (rc != NGP_OK) return rc;
+    if (N == 0) return NGP_OK;
+    nav_run R;
+    rc = nav_run_args("nav_run_occ_backward", rays_o, rays_d, nears, fars, N, num_steps, aabb_host, bg_color3_host, R);
+    if (rc != NGP_OK) return rc;
+    NGP_REQUIRE(grad_image && grad_rays_o && grad_rays_d, "nav_run_occ_backward: null pointer");
+    size_t total;
+    const nro_kept kept = nro_layout(N, num_steps, const_cast<void*>(saved), &total);
+    NGP_REQUIRE(saved && saved_bytes >= total, "nav_run_occ_backward: needs the `saved` buffer its forward filled");
+    hipLaunchKernelGGL(k_nav_run_occ_bwd, dim3(N), dim3(NO_W), sizeof(float) * NV_H * NO_W, (hipStream_t)stream, P, R, grad_image, grad_depth,
+                       grad_weights_sum, kept, grad_rays_o, grad_rays_d);
+    NGP_CHECK_LAUNCH("nav_run_occ_backward");
     return NGP_OK;
 }

@@ -16,6 +16,10 @@
 // k_filter_loss_multi and k_filter_step_multi give hypothesis k (blockIdx.y, or blockIdx.x of the step) the slice [k B, (k + 1) B) of every per-ray buffer
 // and run the bodies the single kernels run (nf_ray_of, nf_squared_error, nf_step), so row k is the single run from the same start bit for bit.
 //
+// Occupied sampling (DESIGN.md §3.5 "Occupancy-masked pose filter"): nf_measure takes the renderer's occupancy grid as an optional argument and then renders
+// and differentiates through ngp_nav_run_occ_forward / _backward (nav_field.hip); ngp_filter_iterations_occ and ngp_filter_hessian_occ are the entry points
+// that pass one.  The entry points without a grid keep their code path.
+//
 // The derivative conventions are torch autograd's of the formula as written (nav/math_utils.py:159-174): R = I + sin(a) K + ((1 - cos(a)) K) K,
 // K = hat(r / (1e-10 + a)), a = |r|, with the denominator's dependence on a kept and a zero subgradient of the norm at r = 0.  No gradient flows through
 // near / far (nerf/renderer.py:140-141).  No atomics; every sum runs in a fixed order, so two runs are bit-identical.
@@ -361,9 +365,10 @@ struct nf_ws {
 };
 // K hypotheses of B rays: every per-ray piece holds K B rays, hypothesis k in [k B, (k + 1) B), and the partials K slices of ceil(B / 256).  The pieces
 // and their order are one statement for both entry points' workspaces; K = 1 is the single loop's
-static nf_ws nf_multi_layout(uint32_t K, uint32_t B, uint32_t num_steps, void* base) {
+// occ: the record is the occupancy-masked run's (ngp_nav_run_occ_saved_bytes: the same records plus each ray's count and list); every other piece is unchanged
+static nf_ws nf_multi_layout(uint32_t K, uint32_t B, uint32_t num_steps, void* base, bool occ = false) {
     if (K < 1 || K > NGP_FILTER_MULTI_MAX_K || B < 1 || (uint64_t)K * B > NF_MAX_B || num_steps < 1 || num_steps > NF_MAX_T) return {};   // total 0: a shape no filter call accepts
-    const size_t n = (size_t)K * B, kept = ngp_nav_run_saved_bytes(K * B, num_steps);
+    const size_t n = (size_t)K * B, kept = occ ? ngp_nav_run_occ_saved_bytes(K * B, num_steps) : ngp_nav_run_saved_bytes(K * B, num_steps);
     ngp_carver c(base);
     return {c.take<float>(3 * n), c.take<float>(3 * n), c.take<float>(n), c.take<float>(n), c.take<float>(3 * n), c.take<float>(n), c.take<float>(n),
             c.take<float>(3 * n), c.take<unsigned char>(kept), c.take<float>(3 * n), c.take<float>(3 * n),
@@ -372,6 +377,7 @@ static nf_ws nf_multi_layout(uint32_t K, uint32_t B, uint32_t num_steps, void* b
 static nf_ws nf_layout(uint32_t B, uint32_t num_steps, void* base) { return nf_multi_layout(1, B, num_steps, base); }
 extern "C" size_t ngp_filter_workspace(uint32_t B, uint32_t num_steps) { return nf_layout(B, num_steps, nullptr).total; }
 extern "C" size_t ngp_filter_multi_workspace(uint32_t K, uint32_t B, uint32_t num_steps) { return nf_multi_layout(K, B, num_steps, nullptr).total; }
+extern "C" size_t ngp_filter_occ_workspace(uint32_t K, uint32_t B, uint32_t num_steps) { return nf_multi_layout(K, B, num_steps, nullptr, true).total; }
 
 static int nf_view_of(const char* who, const ngp_filter_cfg_t* c, nf_view& V) {
     NGP_REQUIRE(c, "%s: null cfg", who);
@@ -398,19 +404,22 @@ extern "C" int ngp_filter_rays(const ngp_filter_cfg_t* c, const float* state, co
 // what the two entry points of the loop do before they queue anything, in this order: the view, the shape, the entry point's own null-pointer refusal
 // (`null_refusal`: its message, or NULL where every pointer is there), the workspace, the field (N = 0 validates and launches nothing), and the
 // start state and inverse covariance the last kernel takes as arguments (A.adam is left zeroed).  K hypotheses (1: the single loop and the Hessian) size
-// the workspace, whose size function `ws_fn` names
+// the workspace, whose size function `ws_fn` names.  grid: null for the dense run; else the occupancy-masked run's grid, judged with the field
 static int nf_begin(const char* who, const char* null_refusal, const ngp_nav_field_t* field, const void* prepared, const ngp_filter_cfg_t* c, uint32_t K,
-                    const char* ws_fn, void* workspace, size_t workspace_bytes, void* stream, nf_view& V, nf_ws& w, nf_step_args& A) {
+                    const char* ws_fn, void* workspace, size_t workspace_bytes, void* stream, nf_view& V, nf_ws& w, nf_step_args& A,
+                    const ngp_occ_grid_t* grid = nullptr) {
     const int rc_v = nf_view_of(who, c, V);
     if (rc_v != NGP_OK) return rc_v;
     const uint32_t T = c->num_steps;
     NGP_REQUIRE(T >= 1 && T <= NF_MAX_T, "%s: num_steps = %u; supported 1 <= num_steps <= 4096", who, T);
     NGP_REQUIRE(!null_refusal, "%s", null_refusal);
-    w = nf_multi_layout(K, c->B, T, workspace);
+    w = nf_multi_layout(K, c->B, T, workspace, grid != nullptr);
     if (!workspace || workspace_bytes < w.total)
         return ngp_fail(NGP_EWORKSPACE, "%s: workspace of %zu bytes, needs %s = %zu", who, workspace_bytes, ws_fn, w.total);
-    const int rc_f = ngp_nav_run_forward(field, prepared, w.rays_o, w.rays_d, w.nears, w.fars, 0, T, c->aabb, c->bg, w.image, w.depth, w.weights_sum, w.saved,
-                                         w.saved_bytes, stream);
+    const int rc_f = grid ? ngp_nav_run_occ_forward(field, prepared, grid, w.rays_o, w.rays_d, w.nears, w.fars, 0, T, c->aabb, c->bg, w.image, w.depth,
+                                                    w.weights_sum, nullptr, w.saved, w.saved_bytes, stream)
+                          : ngp_nav_run_forward(field, prepared, w.rays_o, w.rays_d, w.nears, w.fars, 0, T, c->aabb, c->bg, w.image, w.depth, w.weights_sum, w.saved,
+                                                w.saved_bytes, stream);
     if (rc_f != NGP_OK) return rc_f;
     A = {};
     for (int k = 0; k < 12; k++) A.start[k] = c->start_state[k];
@@ -424,22 +433,28 @@ static int nf_launched(const char* who, const char* what) {
 }
 
 // the measurement pass at `state` for one batch: rays -> run forward -> loss -> run backward, queued; leaves grad_rays_o, grad_rays_d and the loss partials in w.
-// K = 0: one state, the single kernels; K >= 1: `state` is [K,12] and the multi kernels fill K slices, with the run kernels launched once over K B rays
+// K = 0: one state, the single kernels; K >= 1: `state` is [K,12] and the multi kernels fill K slices, with the run kernels launched once over K B rays.
+// grid: null = the dense run; else the occupancy-masked pair renders and differentiates (w laid out with occ)
 static int nf_measure(const char* who, const ngp_nav_field_t* field, const void* prepared, const ngp_filter_cfg_t* c, const nf_view& V, const nf_ws& w,
-                      uint32_t K, const float* state, const float* target, const int32_t* batch, void* stream) {
+                      uint32_t K, const float* state, const float* target, const int32_t* batch, void* stream, const ngp_occ_grid_t* grid = nullptr) {
     const uint32_t B = c->B, T = c->num_steps, blocks = ngp_div_up(B, NF_THREADS), N = (K ? K : 1u) * B;
     hipStream_t s = (hipStream_t)stream;
     if (K) hipLaunchKernelGGL(k_filter_rays_multi, dim3(blocks, K), dim3(NF_THREADS), 0, s, V, state, batch, B, w.rays_o, w.rays_d, w.nears, w.fars);
     else hipLaunchKernelGGL(k_filter_rays, dim3(blocks), dim3(NF_THREADS), 0, s, V, state, batch, B, w.rays_o, w.rays_d, w.nears, w.fars);
     int rc = nf_launched(who, "rays");
     if (rc != NGP_OK) return rc;
-    rc = ngp_nav_run_forward(field, prepared, w.rays_o, w.rays_d, w.nears, w.fars, N, T, c->aabb, c->bg, w.image, w.depth, w.weights_sum, w.saved,
-                             w.saved_bytes, stream);
+    rc = grid ? ngp_nav_run_occ_forward(field, prepared, grid, w.rays_o, w.rays_d, w.nears, w.fars, N, T, c->aabb, c->bg, w.image, w.depth, w.weights_sum,
+                                        nullptr, w.saved, w.saved_bytes, stream)
+              : ngp_nav_run_forward(field, prepared, w.rays_o, w.rays_d, w.nears, w.fars, N, T, c->aabb, c->bg, w.image, w.depth, w.weights_sum, w.saved,
+                                    w.saved_bytes, stream);
     if (rc != NGP_OK) return rc;
     if (K) hipLaunchKernelGGL(k_filter_loss_multi, dim3(blocks, K), dim3(NF_THREADS), 0, s, (const float*)w.image, target, batch, B, c->H, c->W, w.grad_image, w.partials);
     else hipLaunchKernelGGL(k_filter_loss, dim3(blocks), dim3(NF_THREADS), 0, s, (const float*)w.image, target, batch, B, c->H, c->W, w.grad_image, w.partials);
     rc = nf_launched(who, "loss");
     if (rc != NGP_OK) return rc;
+    if (grid)
+        return ngp_nav_run_occ_backward(field, prepared, grid, w.rays_o, w.rays_d, w.nears, w.fars, N, T, c->aabb, c->bg, w.grad_image, nullptr, nullptr,
+                                        w.saved, w.saved_bytes, w.grad_rays_o, w.grad_rays_d, stream);
     return ngp_nav_run_backward(field, prepared, w.rays_o, w.rays_d, w.nears, w.fars, N, T, c->aabb, c->bg, w.grad_image, nullptr, nullptr, w.saved,
                                 w.saved_bytes, w.grad_rays_o, w.grad_rays_d, stream);
 }
@@ -467,32 +482,51 @@ extern "C" int ngp_filter_iterations(const ngp_nav_field_t* field, const void* p
     return NGP_OK;
 }
 
-extern "C" int ngp_filter_iterations_multi(const ngp_nav_field_t* field, const void* prepared, const ngp_filter_cfg_t* c, uint32_t K, float* states,
-                                           float* adam_states, const float* target, const int32_t* batches, uint32_t first_iter, uint32_t n_iter, int update,
-                                           float* losses, float* states_out, float* grads_out, void* workspace, size_t workspace_bytes, void* stream) {
-    NGP_REQUIRE(K >= 1 && K <= NGP_FILTER_MULTI_MAX_K, "filter_iterations_multi: K = %u hypotheses; supported 1 <= K <= %u", K, NGP_FILTER_MULTI_MAX_K);
-    NGP_REQUIRE(!c || c->B > NF_MAX_B || (uint64_t)K * c->B <= NF_MAX_B, "filter_iterations_multi: K * B = %u * %u rays per iteration; supported K * B <= 2^20",
+// the K-hypothesis loop: ngp_filter_iterations_multi (grid null) and ngp_filter_iterations_occ (the grid given); `who` names the entry point in every
+// refusal, `null_refusal` and `ws_fn` are its own words
+static int nf_iterations_multi(const char* who, const char* null_refusal, const char* ws_fn, const ngp_nav_field_t* field, const void* prepared,
+                               const ngp_filter_cfg_t* c, const ngp_occ_grid_t* grid, uint32_t K, float* states, float* adam_states, const float* target,
+                               const int32_t* batches, uint32_t first_iter, uint32_t n_iter, int update, float* losses, float* states_out, float* grads_out,
+                               void* workspace, size_t workspace_bytes, void* stream) {
+    NGP_REQUIRE(K >= 1 && K <= NGP_FILTER_MULTI_MAX_K, "%s: K = %u hypotheses; supported 1 <= K <= %u", who, K, NGP_FILTER_MULTI_MAX_K);
+    NGP_REQUIRE(!c || c->B > NF_MAX_B || (uint64_t)K * c->B <= NF_MAX_B, "%s: K * B = %u * %u rays per iteration; supported K * B <= 2^20", who,
                 K, c ? c->B : 0u);
     nf_view V;
     nf_ws w;
     nf_step_args A;
-    int rc = nf_begin("filter_iterations_multi",
-                      states && adam_states && target && batches ? nullptr : "filter_iterations_multi: null states / adam_states / target / batches", field,
-                      prepared, c, K, "ngp_filter_multi_workspace(K, B, num_steps)", workspace, workspace_bytes, stream, V, w, A);
+    int rc = nf_begin(who, states && adam_states && target && batches ? nullptr : null_refusal, field, prepared, c, K, ws_fn, workspace, workspace_bytes,
+                      stream, V, w, A, grid);
     if (rc != NGP_OK) return rc;
     A.adam = ngp_adam_fill(c->lr, c->beta1, c->beta2, c->eps);
     const uint32_t B = c->B, blocks = ngp_div_up(B, NF_THREADS);
     for (uint32_t k = 0; k < n_iter; k++) {
         const int32_t* batch = batches + 2 * (size_t)B * ((size_t)first_iter + k);
-        rc = nf_measure("filter_iterations_multi", field, prepared, c, V, w, K, states, target, batch, stream);
+        rc = nf_measure(who, field, prepared, c, V, w, K, states, target, batch, stream, grid);
         if (rc != NGP_OK) return rc;
         const size_t row = (size_t)k * K;
         hipLaunchKernelGGL(k_filter_step_multi, dim3(K), dim3(NF_THREADS), 0, (hipStream_t)stream, V, A, update, states, adam_states, batch, B,
                            (const float*)w.grad_rays_o, (const float*)w.grad_rays_d, (const float*)w.partials, blocks, losses ? losses + row : (float*)nullptr,
                            states_out ? states_out + 12 * row : (float*)nullptr, grads_out ? grads_out + 12 * row : (float*)nullptr);
-        NGP_CHECK_LAUNCH("filter_iterations_multi: step");
+        { const int rc_s = nf_launched(who, "step"); if (rc_s != NGP_OK) return rc_s; }
     }
     return NGP_OK;
+}
+
+extern "C" int ngp_filter_iterations_multi(const ngp_nav_field_t* field, const void* prepared, const ngp_filter_cfg_t* c, uint32_t K, float* states,
+                                           float* adam_states, const float* target, const int32_t* batches, uint32_t first_iter, uint32_t n_iter, int update,
+                                           float* losses, float* states_out, float* grads_out, void* workspace, size_t workspace_bytes, void* stream) {
+    return nf_iterations_multi("filter_iterations_multi", "filter_iterations_multi: null states / adam_states / target / batches",
+                               "ngp_filter_multi_workspace(K, B, num_steps)", field, prepared, c, nullptr, K, states, adam_states, target, batches, first_iter,
+                               n_iter, update, losses, states_out, grads_out, workspace, workspace_bytes, stream);
+}
+
+extern "C" int ngp_filter_iterations_occ(const ngp_nav_field_t* field, const void* prepared, const ngp_filter_cfg_t* c, const ngp_occ_grid_t* grid, uint32_t K,
+                                         float* states, float* adam_states, const float* target, const int32_t* batches, uint32_t first_iter, uint32_t n_iter,
+                                         int update, float* losses, float* states_out, float* grads_out, void* workspace, size_t workspace_bytes, void* stream) {
+    NGP_REQUIRE(grid, "filter_iterations_occ: null occupancy grid");
+    return nf_iterations_multi("filter_iterations_occ", "filter_iterations_occ: null states / adam_states / target / batches",
+                               "ngp_filter_occ_workspace(K, B, num_steps)", field, prepared, c, grid, K, states, adam_states, target, batches, first_iter,
+                               n_iter, update, losses, states_out, grads_out, workspace, workspace_bytes, stream);
 }
 
 static int nf_select_args(const char* who, const float* losses, const float* states, uint32_t K, float* best_state, float* best_loss, uint32_t* best_index) {
@@ -625,19 +659,33 @@ extern "C" int ngp_filter_propagate(const ngp_filter_dyn_t* dyn, const float* st
     return NGP_OK;
 }
 
-extern "C" int ngp_filter_hessian(const ngp_nav_field_t* field, const void* prepared, const ngp_filter_cfg_t* c, const float* state, const float* target,
-                                  const int32_t* batch, float* hessian, float* grad, float* loss, float* dLdP, void* workspace, size_t workspace_bytes,
-                                  void* stream) {
+static int nf_hessian(const char* who, const char* null_refusal, const char* ws_fn, const ngp_nav_field_t* field, const void* prepared,
+                      const ngp_filter_cfg_t* c, const ngp_occ_grid_t* grid, const float* state, const float* target, const int32_t* batch, float* hessian,
+                      float* grad, float* loss, float* dLdP, void* workspace, size_t workspace_bytes, void* stream) {
     nf_view V;
     nf_ws w;
     nf_step_args A;
-    int rc = nf_begin("filter_hessian", state && target && batch && hessian ? nullptr : "filter_hessian: null state / target / batch / hessian", field,
-                      prepared, c, 1, "ngp_filter_workspace(B, num_steps)", workspace, workspace_bytes, stream, V, w, A);
+    int rc = nf_begin(who, state && target && batch && hessian ? nullptr : null_refusal, field, prepared, c, 1, ws_fn, workspace, workspace_bytes, stream, V, w,
+                      A, grid);
     if (rc != NGP_OK) return rc;
-    rc = nf_measure("filter_hessian", field, prepared, c, V, w, 0, state, target, batch, stream);
+    rc = nf_measure(who, field, prepared, c, V, w, 0, state, target, batch, stream, grid);
     if (rc != NGP_OK) return rc;
     hipLaunchKernelGGL(k_filter_hessian, dim3(1), dim3(NF_THREADS), 0, (hipStream_t)stream, V, A, state, batch, c->B, (const float*)w.grad_rays_o,
                        (const float*)w.grad_rays_d, (const float*)w.partials, ngp_div_up(c->B, NF_THREADS), hessian, grad, loss, dLdP);
-    NGP_CHECK_LAUNCH("filter_hessian: hessian");
-    return NGP_OK;
+    return nf_launched(who, "hessian");
+}
+
+extern "C" int ngp_filter_hessian(const ngp_nav_field_t* field, const void* prepared, const ngp_filter_cfg_t* c, const float* state, const float* target,
+                                  const int32_t* batch, float* hessian, float* grad, float* loss, float* dLdP, void* workspace, size_t workspace_bytes,
+                                  void* stream) {
+    return nf_hessian("filter_hessian", "filter_hessian: null state / target / batch / hessian", "ngp_filter_workspace(B, num_steps)", field, prepared, c,
+                      nullptr, state, target, batch, hessian, grad, loss, dLdP, workspace, workspace_bytes, stream);
+}
+
+extern "C" int ngp_filter_hessian_occ(const ngp_nav_field_t* field, const void* prepared, const ngp_filter_cfg_t* c, const ngp_occ_grid_t* grid,
+                                      const float* state, const float* target, const int32_t* batch, float* hessian, float* grad, float* loss, float* dLdP,
+                                      void* workspace, size_t workspace_bytes, void* stream) {
+    NGP_REQUIRE(grid, "filter_hessian_occ: null occupancy grid");
+    return nf_hessian("filter_hessian_occ", "filter_hessian_occ: null state / target / batch / hessian", "ngp_filter_occ_workspace(1, B, num_steps)", field,
+                      prepared, c, grid, state, target, batch, hessian, grad, loss, dLdP, workspace, workspace_bytes, stream);
 }

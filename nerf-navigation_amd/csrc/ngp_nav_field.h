@@ -117,30 +117,32 @@ __device__ __forceinline__ bool nv_normalise(const nav_params& P, float wx, floa
 // y[j] = sum_k W[k][j] x[k] for j < NOUT: a rolled loop over the reduction index k, x[k] read from this lane's LDS column, the NOUT
 // accumulators in registers with compile-time indices, row k of W (NOUT contiguous floats) through the scalar cache.  One row is at
 // most 64 SGPRs, so nothing spills; the loop stays rolled so that no more than one row is ever in flight.
-template <int NIN, int NOUT>
+// S: the stride between a column's entries, i.e. the lanes that share the scratch -- NV_BLOCK for the one-workgroup-per-ray and per-point kernels, 64 for
+// the one-wave-per-ray kernels (k_nav_run_occ_*); the same parameter on every helper below that touches the column.
+template <int NIN, int NOUT, uint32_t S = NV_BLOCK>
 __device__ __forceinline__ void nv_matvec(nv_wptr W, const float* __restrict__ col, float (&y)[NOUT]) {
     #pragma unroll
     for (int j = 0; j < NOUT; j++) y[j] = 0.0f;
     #pragma unroll 1
     for (int k = 0; k < NIN; k++) {
-        const float a = col[k * NV_BLOCK];
+        const float a = col[k * S];
         const nv_wptr w = W + k * NOUT;
         #pragma unroll
         for (int j = 0; j < NOUT; j++) y[j] = __builtin_fmaf(w[j], a, y[j]);
     }
 }
 
-template <int N>
+template <uint32_t S = NV_BLOCK, int N>
 __device__ __forceinline__ void nv_park(const float (&v)[N], float* __restrict__ col, int at = 0) {
     #pragma unroll
-    for (int k = 0; k < N; k++) col[(at + k) * NV_BLOCK] = v[k];
+    for (int k = 0; k < N; k++) col[(at + k) * S] = v[k];
 }
 
-template <int N>
+template <uint32_t S = NV_BLOCK, int N>
 __device__ __forceinline__ uint64_t nv_park_relu(const float (&v)[N], float* __restrict__ col) {       // relu(v) into the column; returns the mask
     uint64_t m = 0;
     #pragma unroll
-    for (int k = 0; k < N; k++) { col[k * NV_BLOCK] = fmaxf(v[k], 0.0f); m |= (uint64_t)(v[k] > 0.0f) << k; }
+    for (int k = 0; k < N; k++) { col[k * S] = fmaxf(v[k], 0.0f); m |= (uint64_t)(v[k] > 0.0f) << k; }
     return m;
 }
 
@@ -166,23 +168,23 @@ __device__ __forceinline__ void nv_hidden(const nav_params& P, bool inside, floa
 }
 
 // density net forward for one point: out[16] = W2 . relu(W1 . enc(x)); returns the ReLU mask of the hidden layer
-template <int U = 1>
+template <int U = 1, uint32_t S = NV_BLOCK>
 __device__ __forceinline__ uint64_t nv_density_forward(const nav_params& P, bool inside, float x0, float x1, float x2, float* __restrict__ col,
                                                        float (&out)[16]) {
     float h[NV_H];
     nv_hidden<U>(P, inside, x0, x1, x2, h);
-    const uint64_t relu = nv_park_relu(h, col);
-    nv_matvec<NV_H, 16>(P.w2t, col, out);
+    const uint64_t relu = nv_park_relu<S>(h, col);
+    nv_matvec<NV_H, 16, S>(P.w2t, col, out);
     return relu;
 }
 
 // backward of the density net for one point: gout[16] = d L / d out, `relu` = which hidden units were active  ->  d L / d (world position)
-template <int U = 1>
+template <int U = 1, uint32_t S = NV_BLOCK>
 __device__ __forceinline__ void nv_density_backward(const nav_params& P, bool inside, float x0, float x1, float x2, uint64_t relu,
                                                     const float (&gout)[16], float* __restrict__ col, float& gx, float& gy, float& gz) {
     float gh[NV_H];                                                      // d L / d h (ReLU mask applied)
-    nv_park(gout, col);
-    nv_matvec<16, NV_H>(P.w2, col, gh);
+    nv_park<S>(gout, col);
+    nv_matvec<16, NV_H, S>(P.w2, col, gh);
     #pragma unroll
     for (int j = 0; j < NV_H; j++) gh[j] = ((relu >> j) & 1ull) ? gh[j] : 0.0f;
     float ax = 0.0f, ay = 0.0f, az = 0.0f;
@@ -235,21 +237,22 @@ __device__ __forceinline__ void nv_sh_backward(const nav_params& P, float x, flo
 }
 
 // colour forward for one sample; returns the ReLU masks of the two hidden layers and the pre-sigmoid... no: rgb after the sigmoid
+template <uint32_t S = NV_BLOCK>
 __device__ __forceinline__ void nv_color_forward(const nav_params& P, float dxr, float dyr, float dzr, const float (&geo)[NV_GEO],
                                                  float* __restrict__ col, float (&rgb)[3], uint64_t& mask_a, uint64_t& mask_b) {
     {
         float sh[16];
         nv_sh(P, dxr, dyr, dzr, sh);
-        nv_park(sh, col);
-        nv_park(geo, col, 16);
+        nv_park<S>(sh, col);
+        nv_park<S>(geo, col, 16);
     }
     float hid[NV_H];
-    nv_matvec<NV_CIN, NV_H>(P.v0t, col, hid);
-    mask_a = nv_park_relu(hid, col);
-    nv_matvec<NV_H, NV_H>(P.v1t, col, hid);
-    mask_b = nv_park_relu(hid, col);
+    nv_matvec<NV_CIN, NV_H, S>(P.v0t, col, hid);
+    mask_a = nv_park_relu<S>(hid, col);
+    nv_matvec<NV_H, NV_H, S>(P.v1t, col, hid);
+    mask_b = nv_park_relu<S>(hid, col);
     float o[3];
-    nv_matvec<NV_H, 3>(P.v2t, col, o);
+    nv_matvec<NV_H, 3, S>(P.v2t, col, o);
     #pragma unroll
     for (int c = 0; c < 3; c++) rgb[c] = 1.0f / (1.0f + expf(-o[c]));
 }

@@ -330,6 +330,72 @@ class _nav_run(torch.autograd.Function):
         return go, gd, None, None, None
 
 
+def occupancy_grid(renderer):
+    """(ngp_occ_grid_t, bitfield tensor) of a renderer built with cuda_ray=True: its density_bitfield, cascade and grid_size, what the frame kernels march
+    through.  The struct holds the tensor's pointer: keep the tensor alive as long as the struct is used."""
+    import ngp_hip as _hip
+    if not getattr(renderer, "cuda_ray", False) or getattr(renderer, "density_bitfield", None) is None:
+        raise ValueError("occupied sampling needs the renderer's occupancy grid: build the renderer with cuda_ray=True")
+    bits = renderer.density_bitfield
+    C, H = int(renderer.cascade), int(renderer.grid_size)
+    if not (bits.is_cuda and bits.dtype == torch.uint8 and bits.is_contiguous() and bits.numel() * 8 == C * H ** 3):
+        raise ValueError(f"density_bitfield must be a contiguous uint8 tensor of {C} * {H}^3 / 8 bytes on the GPU")
+    return _hip.ngp_occ_grid_t(bits.data_ptr(), C, H), bits
+
+
+class _nav_run_occ(torch.autograd.Function):
+    """_nav_run with the occupancy grid consulted (ngp_nav_run_occ_forward / _backward): the sigma of every lattice sample whose occupancy bit is clear is
+    zero, and the field is evaluated at the occupied samples only.  The mask is a constant of the float32 sample position, so the gradients to the rays
+    are the masked function's exact derivatives; second derivatives as for _nav_run.  `counts`: an int32 [N] tensor to receive each ray's occupied
+    sample count, or None."""
+
+    @staticmethod
+    def forward(ctx, rays_o, rays_d, owner, num_steps, bg, counts=None):
+        import ctypes
+        import raymarching
+        import ngp_hip as _hip
+        rays_o, rays_d = rays_o.contiguous().float(), rays_d.contiguous().float()
+        N = rays_o.shape[0]
+        ren = owner.renderer
+        grid, bits = occupancy_grid(ren)
+        if counts is not None and not (counts.is_cuda and counts.dtype == torch.int32 and counts.is_contiguous() and counts.numel() == N):
+            raise ValueError(f"counts must be a contiguous int32 [{N}] tensor on the GPU")
+        nears, fars = raymarching.near_far_from_aabb(rays_o, rays_d, ren._aabb(), ren.min_near)
+        aabb = (ctypes.c_float * 6)(*ren._aabb_host())
+        bgc = (ctypes.c_float * 3)(*bg)
+        image = torch.empty(N, 3, dtype=torch.float32, device=rays_o.device)
+        depth = torch.empty(N, dtype=torch.float32, device=rays_o.device)
+        ws = torch.empty(N, dtype=torch.float32, device=rays_o.device)
+        st, prep = owner.struct()
+        L = _hip.lib()
+        need = any(ctx.needs_input_grad[:2])
+        saved = _hip.workspace(L.ngp_nav_run_occ_saved_bytes(N, int(num_steps)), rays_o.device) if need else None
+        with torch.cuda.device(rays_o.device), _hip.timed("nav_run_occ_forward"):
+            _hip.check(L.ngp_nav_run_occ_forward(ctypes.byref(st), _hip.ptr(prep), ctypes.byref(grid), _hip.ptr(rays_o), _hip.ptr(rays_d), _hip.ptr(nears),
+                                                 _hip.ptr(fars), N, int(num_steps), aabb, bgc, _hip.ptr(image), _hip.ptr(depth), _hip.ptr(ws),
+                                                 _hip.ptr(counts), _hip.ptr(saved), saved.numel() if need else 0, _hip.stream()), "nav_run_occ_forward")
+        ctx.save_for_backward(rays_o, rays_d, nears, fars, saved if need else torch.empty(0, device=rays_o.device), bits)
+        ctx.owner, ctx.num_steps, ctx.bg, ctx.aabb, ctx.grid = owner, int(num_steps), bgc, aabb, grid
+        return image, depth, ws
+
+    @staticmethod
+    def backward(ctx, g_image, g_depth, g_ws):
+        import ctypes
+        import ngp_hip as _hip
+        rays_o, rays_d, nears, fars, saved, _bits = ctx.saved_tensors
+        g_image, g_depth, g_ws = g_image.detach(), g_depth.detach(), g_ws.detach()
+        N = rays_o.shape[0]
+        go, gd = torch.empty_like(rays_o), torch.empty_like(rays_d)
+        st, prep = ctx.owner.struct()
+        with torch.cuda.device(rays_o.device), _hip.timed("nav_run_occ_backward"):
+            _hip.check(_hip.lib().ngp_nav_run_occ_backward(ctypes.byref(st), _hip.ptr(prep), ctypes.byref(ctx.grid), _hip.ptr(rays_o), _hip.ptr(rays_d),
+                                                           _hip.ptr(nears), _hip.ptr(fars), N, ctx.num_steps, ctx.aabb, ctx.bg,
+                                                           _hip.ptr(g_image.contiguous().float()), _hip.ptr(g_depth.contiguous().float()),
+                                                           _hip.ptr(g_ws.contiguous().float()), _hip.ptr(saved), saved.numel(), _hip.ptr(go), _hip.ptr(gd),
+                                                           _hip.stream()), "nav_run_occ_backward")
+        return go, gd, None, None, None, None
+
+
 class NativeNavQueries(NavQueries):
     """NavQueries on the fused float32 kernels (csrc/nav_field.hip): `density_fn` = one launch (+ one for its gradient), `render_fn` = one
     launch per max_ray_batch rays (+ one for the gradient to the rays) instead of ~130 launches per filter iteration.  Same interface and
@@ -375,6 +441,20 @@ class NativeNavQueries(NavQueries):
                 images.append(img)
                 depths.append(dep)
         return {"image": torch.cat(images).view(B, N, 3), "depth": torch.cat(depths).view(B, N)}
+
+    def render_fn_occupied(self, rays_o, rays_d, counts=None):
+        """rays [N,3] -> (image [N,3], depth [N], weights_sum [N]) of the run with the renderer's occupancy grid consulted: the sigma of every lattice sample
+        in an empty grid cell is zero and the field is evaluated at the occupied samples only (DESIGN 3.5 "Occupancy-masked pose filter"); gradients to
+        the rays.  ValueError unless the renderer was built with cuda_ray=True.  counts: an int32 [N] tensor for each ray's occupied sample count."""
+        occupancy_grid(self.renderer)
+        images, depths, sums = [], [], []
+        N = rays_o.shape[0]
+        for head in range(0, N, self.max_ray_batch):
+            tail = min(head + self.max_ray_batch, N)
+            img, dep, ws = _nav_run_occ.apply(rays_o[head:tail], rays_d[head:tail], self.native, self.num_steps, (1.0, 1.0, 1.0),
+                                              None if counts is None else counts[head:tail])
+            images.append(img); depths.append(dep); sums.append(ws)
+        return torch.cat(images), torch.cat(depths), torch.cat(sums)
 
 
 # ------------------------------------------------------------------------------------------------------------------------
@@ -937,7 +1017,17 @@ def nearest_pd(A):
     return P
 
 
-class NativePoseFilter:
+class _KeywordSampling(type):
+    """NativePoseFilter(..., sampling=...): a keyword-only option taken here, so that the constructor's positional parameters (filter_cfg, queries,
+    start_state, agent_cfg -- in that order, agent_cfg last) stay what their callers and tests/test_filter_step_host.py rely on."""
+
+    def __call__(cls, *args, sampling="dense", **kwargs):
+        self = super().__call__(*args, **kwargs)
+        self.set_sampling(sampling)
+        return self
+
+
+class NativePoseFilter(metaclass=_KeywordSampling):
     """Estimator (nav/estimator_helpers.py) with its optimisation loop native: measurement_fn -> backward -> Adam run as ngp_filter_iterations, i.e. per
     iteration one launch for the batch's rays from the state, NativeNavQueries' run kernel forward, one launch for the loss, the run kernel backward
     and one launch for the chain back to the state, the Mahalanobis term and the Adam step.  `filter_cfg` takes the reference's keys batch_size,
@@ -966,11 +1056,17 @@ class NativePoseFilter:
     sequence of five launches per iteration, the best final objective kept on the device; hypothesis k is bit for bit the single run from its start.
 
         xt = filt.estimate_state(target, action, interest_regions, rng=rng, offsets=offsets)   # offsets [K,12] around the propagated state
+
+    sampling="occupied" (DESIGN 3.5 "Occupancy-masked pose filter"): every measurement pass -- the loop, the multi-start loop, cost_and_gradient, the
+    Hessian, and so estimate_state -- renders through the renderer's occupancy grid (ngp_filter_iterations_occ / ngp_filter_hessian_occ): the sigma of a
+    lattice sample in an empty grid cell is zero and the field is evaluated at the occupied samples only.  A different objective from the dense one
+    (the sensor's model of empty space); needs a renderer built with cuda_ray=True.  The default "dense" is the route above, unchanged.
     """
 
     def __init__(self, filter_cfg, queries, start_state=None, agent_cfg=None):
         if not isinstance(queries, NativeNavQueries):
             raise ValueError(f"NativePoseFilter needs a NativeNavQueries (the fused float32 queries), got {type(queries).__name__}")
+        self.sampling = "dense"                              # the keyword `sampling` arrives through set_sampling (_KeywordSampling)
         self.queries = queries
         self.device = queries.native.field.encoder.embeddings.device
         self.cfg = filter_cfg
@@ -988,7 +1084,15 @@ class NativePoseFilter:
         self.hessian_grad = self.hessian_loss = self.hessian_dLdP = None
         self._feat_ws = self._seed0 = None
         self.multi = None                                    # the hypotheses of the last multi-start run (estimate_relative_pose_multi)
-        self._ws_multi = None
+        self._ws_multi = self._ws_occ = None
+
+    def set_sampling(self, sampling):
+        """"dense": every sample of the lattice (the default route); "occupied": the samples in occupied grid cells only (the class docstring)"""
+        if sampling not in ("dense", "occupied"):
+            raise ValueError(f"sampling must be 'dense' or 'occupied', got {sampling!r}")
+        if sampling == "occupied":
+            occupancy_grid(self.queries.renderer)            # ValueError unless the renderer holds a grid (cuda_ray=True)
+        self.sampling = sampling
 
     # -- plumbing ------------------------------------------------------------------------------------------------------
     def _vec(self, v):
@@ -1040,6 +1144,17 @@ class NativePoseFilter:
             self._ws = _hip.workspace(nbytes, self.device)
         return self._ws
 
+    def _workspace_occ(self, K, B):
+        """the workspace of the occupied route (one buffer, grown on demand) and the grid's struct with the tensor it points into"""
+        import ngp_hip as _hip
+        nbytes = _hip.lib().ngp_filter_occ_workspace(int(K), int(B), int(self.queries.num_steps))
+        if nbytes == 0:
+            raise ValueError(f"{K} hypotheses of {B} rays: supported 1 <= K <= {_hip.FILTER_MULTI_MAX_K} and K * B <= 2^20")
+        if self._ws_occ is None or self._ws_occ.numel() < nbytes:
+            self._ws_occ = _hip.workspace(nbytes, self.device)
+        grid, bits = occupancy_grid(self.queries.renderer)
+        return self._ws_occ, grid, bits
+
     def new_adam_state(self):
         """zeroed Adam moments and step: the reference builds a new optimiser in every estimate_relative_pose"""
         import ngp_hip as _hip
@@ -1065,6 +1180,13 @@ class NativePoseFilter:
         target = self._target(target)
         st, prep = self.queries.native.struct()
         c = self._cfg_struct(B, start_state, sig)
+        if self.sampling == "occupied":                      # K = 1 of the occupied loop: state [12] is states [1,12], losses [n] is [n,1]
+            ws, grid, bits = self._workspace_occ(1, B)
+            _hip.check(_hip.lib().ngp_filter_iterations_occ(ctypes.byref(st), _hip.ptr(prep), ctypes.byref(c), ctypes.byref(grid), 1, _hip.ptr(state),
+                                                            _hip.ptr(adam_state), _hip.ptr(target), _hip.ptr(batches), int(first_iter), int(n_iter),
+                                                            1 if update else 0, _hip.ptr(losses), _hip.ptr(states), _hip.ptr(grads), _hip.ptr(ws),
+                                                            ws.numel(), _hip.stream()), "filter_iterations_occ")
+            return
         ws = self._workspace(B)
         _hip.check(_hip.lib().ngp_filter_iterations(ctypes.byref(st), _hip.ptr(prep), ctypes.byref(c), _hip.ptr(state), _hip.ptr(adam_state),
                                                     _hip.ptr(target), _hip.ptr(batches), int(first_iter), int(n_iter), 1 if update else 0,
@@ -1222,6 +1344,13 @@ class NativePoseFilter:
         import ngp_hip as _hip
         K, B = int(states.shape[0]), int(batches.shape[1])
         st, prep = self.queries.native.struct()
+        if self.sampling == "occupied":
+            ws, grid, bits = self._workspace_occ(K, B)
+            _hip.check(_hip.lib().ngp_filter_iterations_occ(ctypes.byref(st), _hip.ptr(prep), ctypes.byref(c), ctypes.byref(grid), K, _hip.ptr(states),
+                                                            _hip.ptr(adam_states), _hip.ptr(target), _hip.ptr(batches), int(first_iter), int(n_iter),
+                                                            1 if update else 0, _hip.ptr(losses), _hip.ptr(states_out), _hip.ptr(grads), _hip.ptr(ws),
+                                                            ws.numel(), _hip.stream()), "filter_iterations_occ")
+            return
         ws = self._workspace_multi(K, B)
         _hip.check(_hip.lib().ngp_filter_iterations_multi(ctypes.byref(st), _hip.ptr(prep), ctypes.byref(c), K, _hip.ptr(states), _hip.ptr(adam_states),
                                                           _hip.ptr(target), _hip.ptr(batches), int(first_iter), int(n_iter), 1 if update else 0,
@@ -1344,6 +1473,14 @@ class NativePoseFilter:
         out = dict(hessian=torch.empty(12, 12, **kw), grad=torch.empty(12, **kw), loss=torch.empty(1, **kw), dLdP=torch.empty(3, 3, **kw))
         st, prep = self.queries.native.struct()
         c = self._cfg_struct(B, start_state, sig)
+        if self.sampling == "occupied":
+            ws, grid, bits = self._workspace_occ(1, B)
+            _hip.check(_hip.lib().ngp_filter_hessian_occ(ctypes.byref(st), _hip.ptr(prep), ctypes.byref(c), ctypes.byref(grid),
+                                                         _hip.ptr(self._vec(state).contiguous()), _hip.ptr(target), _hip.ptr(batch), _hip.ptr(out["hessian"]),
+                                                         _hip.ptr(out["grad"]), _hip.ptr(out["loss"]), _hip.ptr(out["dLdP"]), _hip.ptr(ws), ws.numel(),
+                                                         _hip.stream()), "filter_hessian_occ")
+            out["loss"] = out["loss"][0]
+            return out
         ws = self._workspace(B)
         _hip.check(_hip.lib().ngp_filter_hessian(ctypes.byref(st), _hip.ptr(prep), ctypes.byref(c), _hip.ptr(self._vec(state).contiguous()),
                                                  _hip.ptr(target), _hip.ptr(batch), _hip.ptr(out["hessian"]), _hip.ptr(out["grad"]), _hip.ptr(out["loss"]),
@@ -1621,7 +1758,7 @@ SIMULATE_FOLDERS = ("init_poses", "init_costs", "replan_poses", "replan_costs", 
 
 
 def simulate(planner_cfg, agent_cfg, filter_cfg, extra_cfg, queries, sensor=None, basefolder=None, generator=None, interest_regions=None, seed=None,
-             filter_offsets=None, planner_starts=None):
+             filter_offsets=None, planner_starts=None, filter_sampling="dense"):
     """simulate.simulate (simulate.py:18-102) over the native planner, agent and filter: A* and learn_init, then per MPC step the planner's action, the agent's
     noisy step and observation, the filter's time step and, before `steps - 5`, update_state and learn_update.
 
@@ -1631,6 +1768,7 @@ def simulate(planner_cfg, agent_cfg, filter_cfg, extra_cfg, queries, sensor=None
     (features="native", the draw keyed by `seed`) unless interest_regions ([M,2] (row, col)) are given, which are then used every step with
     numpy's default_rng(seed).  seed also seeds a_star_init's path noise; None leaves all three to the global / operating-system sources, as the reference.
     filter_offsets [K,12]: every time step of the filter is the multi-start one (estimate_state's `offsets`); None: the loop as it is.
+    filter_sampling: NativePoseFilter's `sampling` ("dense", or "occupied": the filter renders through the renderer's occupancy grid).
     planner_starts dict(K=..., amplitude=...): learn_init and every learn_update take the planner's multi-start route from draw_offsets(K, amplitude) at
     the current R, drawn from a generator of their own (seeded by `seed`; the global one when seed is None); None: the loop as it is.
     basefolder: a directory (created when missing) that receives the reference's five sub-folders, init_* and replan_* from the planner, estimator_data/
@@ -1658,7 +1796,7 @@ def simulate(planner_cfg, agent_cfg, filter_cfg, extra_cfg, queries, sensor=None
     start12 = torch.cat([s18[:6], _rot_matrix_to_vec(s18[6:15].reshape(3, 3)), s18[15:]], dim=-1).to(traj.device)
     agent_cfg = dict(agent_cfg, x0=start12)
     agent = NativeAgent(agent_cfg, queries, sensor)
-    filt = NativePoseFilter(filter_cfg, queries, start12, agent_cfg)
+    filt = NativePoseFilter(filter_cfg, queries, start12, agent_cfg, sampling=filter_sampling)
     steps = int(traj.get_actions().shape[0])
     noise_mean, noise_std = extra_cfg["mpc_noise_mean"], extra_cfg["mpc_noise_std"]
     rng = None if interest_regions is None else np.random.default_rng(seed)

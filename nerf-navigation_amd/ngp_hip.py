@@ -122,6 +122,9 @@ _SIGNATURES = {
     "ngp_nav_run_saved_bytes": (c_sz, [c_u32, c_u32]),
     "ngp_nav_run_forward": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_u32, c_u32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "ngp_nav_run_backward": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_u32, c_u32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp, c_vp, c_vp]),
+    "ngp_nav_run_occ_saved_bytes": (c_sz, [c_u32, c_u32]),
+    "ngp_nav_run_occ_forward": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_u32, c_u32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "ngp_nav_run_occ_backward": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_u32, c_u32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp, c_vp, c_vp]),
     "ngp_nav_render_frame_workspace": (c_sz, [c_u32]),
     "ngp_nav_render_frame": (c_int, [c_vp, c_vp, c_vp, c_vp, c_u32, c_u32, c_vp, c_f32, c_vp, c_u32, c_u32, c_f32, c_u32, c_vp,
                                      c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
@@ -156,6 +159,9 @@ _SIGNATURES = {
     "ngp_filter_select_host": (c_int, [c_vp, c_vp, c_u32, c_vp, c_vp, c_vp]),
     "ngp_filter_propagate": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "ngp_filter_hessian": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "ngp_filter_occ_workspace": (c_sz, [c_u32, c_u32, c_u32]),
+    "ngp_filter_iterations_occ": (c_int, [c_vp, c_vp, c_vp, c_vp, c_u32, c_vp, c_vp, c_vp, c_vp, c_u32, c_u32, c_int, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "ngp_filter_hessian_occ": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "ngp_features_default_cfg": (None, [c_vp]),
     "ngp_features_workspace": (c_sz, [c_u32, c_u32]),
     "ngp_features_layout": (c_int, [c_u32, c_u32, c_vp]),
@@ -218,6 +224,11 @@ class ngp_filter_cfg_t(ctypes.Structure):
     _fields_ = [("H", c_u32), ("W", c_u32), ("intrinsics", c_f32 * 4), ("aabb", c_f32 * 6), ("min_near", c_f32), ("num_steps", c_u32),
                 ("bg", c_f32 * 3), ("B", c_u32), ("start_state", c_f32 * 12), ("sig_inv", c_f32 * 144), ("lr", ctypes.c_double),
                 ("beta1", ctypes.c_double), ("beta2", ctypes.c_double), ("eps", ctypes.c_double)]
+
+
+class ngp_occ_grid_t(ctypes.Structure):
+    """include/ngp_hip.h: ngp_occ_grid_t"""
+    _fields_ = [("bitfield", c_vp), ("C", c_u32), ("Hgrid", c_u32)]
 
 
 class ngp_filter_dyn_t(ctypes.Structure):

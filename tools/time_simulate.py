@@ -50,8 +50,9 @@ def quartiles(v):
     return {"median": round(statistics.median(v), 4), "q1": round(q[0], 4), "q3": round(q[2], 4)}
 
 
-def scene(dev, side):
-    """(queries over the map, sensor renderer with the occupancy grid loaded, the true state)"""
+def scene(dev, side, queries_hold_the_grid=False):
+    """(queries over the map, sensor renderer with the occupancy grid loaded, the true state).  queries_hold_the_grid: the queries' renderer is the
+    sensor's (what NativePoseFilter(sampling="occupied") needs); the dense routes never look at the grid"""
     from ngp import nav
     from ngp import workload as W
     from ngp.field import NGPField
@@ -68,6 +69,8 @@ def scene(dev, side):
     q = nav.NativeNavQueries(ren, W.intrinsics(side, side), side, side, num_steps=STEPS)
     sensor = NGPRenderer(field, bound=W.BOUND, cuda_ray=True, density_thresh=10.0).to(dev).eval()
     sensor.load_density_grid(W.density_grid())
+    if queries_hold_the_grid:
+        q = nav.NativeNavQueries(sensor, W.intrinsics(side, side), side, side, num_steps=STEPS)
     return q, sensor, torch.tensor(TRUE_STATE, device=dev)
 
 
@@ -114,7 +117,7 @@ def group_agent(args, dev):
 def group_filter(args, dev):
     from ngp import nav
     from time_filter import START_OFFSET
-    q, sensor, x0 = scene(dev, args.side)
+    q, sensor, x0 = scene(dev, args.side, queries_hold_the_grid=args.filter_sampling == "occupied")
     cfg = dict(AGENT, I=torch.eye(3), x0=x0)
     agent = nav.NativeAgent(cfg, q, sensor)
     action = torch.tensor(ACTION, device=dev)
@@ -122,7 +125,8 @@ def group_filter(args, dev):
     target = agent.target
     start = x0 + torch.tensor(START_OFFSET, device=dev)
     sig0, Q = 0.1 * torch.eye(12, device=dev), 0.01 * torch.eye(12, device=dev)
-    filt = nav.NativePoseFilter({"batch_size": RAYS, "lrate": 1e-3, "N_iter": args.iters, "sig0": sig0, "Q": Q}, q, start.clone(), cfg)
+    filt = nav.NativePoseFilter({"batch_size": RAYS, "lrate": 1e-3, "N_iter": args.iters, "sig0": sig0, "Q": Q}, q, start.clone(), cfg,
+                                sampling=args.filter_sampling)
 
     # the front (keypoints, dilation, pixel list) is timed on the observation as it is.  The loop needs batch_size distinct pixels: where this synthetic
     # scene gives the detector fewer, the batches are drawn (natively, on the device) from every pixel of the image instead, and the output says so
@@ -143,7 +147,8 @@ def group_filter(args, dev):
     for _ in range(args.rounds):
         times["filter_step"].append(wall(step)[0])
         times["interest_regions"].append(wall(lambda: filt.interest_regions(target))[0])
-    return {"group": "filter", "case": f"{RAYS} rays x {STEPS} steps, {args.iters} iterations, {args.side} x {args.side} target, {args.rounds} rounds",
+    return {"group": "filter", "case": f"{RAYS} rays x {STEPS} steps, {args.iters} iterations, {args.side} x {args.side} target, {args.rounds} rounds, "
+                                       f"{args.filter_sampling} sampling",
             "ms": {k: quartiles(v) for k, v in times.items()}, "interest_pixels": found,
             "batches_drawn_from": "the interest regions (features='native')" if native_front else "every pixel (fewer interest pixels than rays per batch)",
             "loop_ran": bool(len(filt.losses))}
@@ -181,6 +186,7 @@ def main():
     ap.add_argument("--iters", type=int, default=ITERS)
     ap.add_argument("--epochs", type=int, default=EPOCHS)
     ap.add_argument("--limit", type=int, default=300, help="seconds a group may take")
+    ap.add_argument("--filter-sampling", choices=("dense", "occupied"), default="dense", help="NativePoseFilter's sampling in the filter group")
     args = ap.parse_args()
     if args.phase:
         dev = torch.device("cuda:0")
@@ -190,7 +196,7 @@ def main():
     summary = {}
     for group in GROUPS:
         cmd = ["timeout", "-k", "10", str(args.limit), sys.executable, os.path.abspath(__file__), "--phase", group, "--rounds", str(args.rounds), "--side",
-               str(args.side), "--iters", str(args.iters), "--epochs", str(args.epochs)]
+               str(args.side), "--iters", str(args.iters), "--epochs", str(args.epochs), "--filter-sampling", args.filter_sampling]
         done = subprocess.run(cmd, stdout=subprocess.PIPE, text=True)
         sys.stdout.write(done.stdout)
         sys.stdout.flush()

@@ -1,7 +1,8 @@
 """Record what the host side of libngp_hip.so promises about workspaces: every size function over a grid of shapes, the two offsets
 ngp_field_train_live_list hands out, and the return code and message of every entry point that refuses a workspace one byte short before it
 touches the device.  Needs no GPU.  `python tools/workspace_sizes.py` writes tests/golden/workspace_sizes.json from the library NGP_HIP_LIB
-selects (default: the tree's own build); tests/test_workspace_host.py calls collect() on the built library and compares."""
+selects (default: the tree's own build); tests/test_workspace_host.py calls collect() on the built library and compares.  The size functions of the
+occupancy-masked run and filter route have a fixture of their own, tests/golden/workspace_sizes_run_occ.json (tests/test_run_occ_host.py), written too."""
 import ctypes
 import importlib
 import itertools
@@ -47,11 +48,23 @@ SIZE_CALLS = {
     "ngp_plan_workspace": list(itertools.product(PLAN_R, PLAN_B)),
 }
 
+# the occupancy-masked run and the filter route over it (a fixture of their own: the one above is compared whole)
+RUN_OCC_GOLDEN = os.path.join(ROOT, "tests", "golden", "workspace_sizes_run_occ.json")
+RUN_OCC_CALLS = {
+    "ngp_nav_run_occ_saved_bytes": [(0, 64), (16, 0), (1, 1), (1, 64), (8, 64), (16, 257), (152, 257), (8, 513), (8, 4096), (1024, 512), (8192, 512), (3, 4095)],
+    "ngp_filter_occ_workspace": [(1, 16, 64), (3, 16, 64), (64, 16, 64), (1, 64, 64), (3, 64, 64), (1, 1024, 512), (8, 128, 512), (8, 1024, 512), (1, 257, 64),
+                                 (0, 16, 64), (65, 16, 64), (1, 16, 4097)],
+}
+
 LIVE_BASE = 1 << 20            # dummy workspace address: ngp_field_train_live_list only adds offsets to it
 
 
 def sizes(L):
     return {name: [list(a) + [int(getattr(L, name)(*a))] for a in calls] for name, calls in SIZE_CALLS.items()}
+
+
+def run_occ_sizes(L):
+    return {name: [list(a) + [int(getattr(L, name)(*a))] for a in calls] for name, calls in RUN_OCC_CALLS.items()}
 
 
 def live_list(L):
@@ -127,3 +140,7 @@ if __name__ == "__main__":
         json.dump(data, f, indent=0, separators=(",", ":"))
         f.write("\n")
     print("wrote", GOLDEN, "from", H.LIB_PATH)
+    with open(RUN_OCC_GOLDEN, "w") as f:
+        json.dump(run_occ_sizes(H.lib()), f, indent=1)
+        f.write("\n")
+    print("wrote", RUN_OCC_GOLDEN)
