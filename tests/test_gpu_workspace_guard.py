@@ -3,7 +3,15 @@
 `ngp_hip.workspace` is replaced by one that hands out the middle n bytes of a buffer of n + 512 (offset 256, so the alignment the allocator
 gives is kept).  Each op runs through its product wrapper twice, the whole buffer pre-filled with 0xAB and then with 0x00: both 256-byte
 guards must be untouched, and the two runs' outputs must be the same bit for bit.  The shapes are the smallest that put more than one piece
-of the layout and a partial last block into play (csrc/ngp_workspace.h; the layouts themselves are pinned by tests/test_workspace_host.py)."""
+of the layout and a partial last block into play (csrc/ngp_workspace.h; the layouts themselves are pinned by tests/test_workspace_host.py).
+
+Each case's docstring names the block or tile its size is one past, and which launch writes a piece of the workspace before which launch reads
+it: under the 0xAB fill a piece read before it is written is a wild value, so that order was read in csrc/ before the case first ran.
+tests/_guard.py holds the runner and the table of size functions and their cases (tests/test_workspace_table.py keeps it complete).
+
+Not here, because they draw no workspace: NativePlanner.occupancy / find_path / a_star_init (csrc/nav_astar.hip: the lattice and the result | path
+buffer are outputs the wrapper allocates with their exact sizes; the search keeps its labels in LDS) and NativeAgent (csrc/nav_agent.hip: "no
+workspace").  The loss heads' workspace is allocated zeroed by ngp/train.py itself, not through ngp_hip.workspace: its case drives the C ABI."""
 import importlib
 
 import numpy as np
@@ -13,48 +21,8 @@ import torch
 importlib.import_module("nerf-navigation_amd")
 pytestmark = pytest.mark.gpu
 
-GUARD = 256
-
-
-class GuardedWorkspaces:
-    def __init__(self, fill):
-        self.fill, self.buffers = fill, []
-
-    def __call__(self, nbytes, device):
-        n = max(int(nbytes), 16)
-        buf = torch.full((n + 2 * GUARD,), self.fill, dtype=torch.uint8, device=device)
-        assert buf.data_ptr() % 256 == 0
-        self.buffers.append(buf)
-        return buf[GUARD:GUARD + n]
-
-    def check(self, at_least):
-        assert len(self.buffers) >= at_least, f"{len(self.buffers)} workspaces were allocated through ngp_hip.workspace, expected {at_least}"
-        for k, buf in enumerate(self.buffers):
-            assert bool((buf[:GUARD] == self.fill).all()), f"workspace {k} ({buf.numel() - 2 * GUARD} bytes): written in front of it"
-            assert bool((buf[-GUARD:] == self.fill).all()), f"workspace {k} ({buf.numel() - 2 * GUARD} bytes): written behind it"
-
-
-@pytest.fixture
-def guarded(monkeypatch, dev):
-    """guarded(op, at_least): runs op() under both fills, checks the guards of the (at least `at_least`) workspaces it allocated and that its
-    outputs (a list of tensors) do not depend on the fill; returns the outputs"""
-    import ngp_hip
-
-    def run(op, at_least=1):
-        outs = []
-        for fill in (0xAB, 0x00):
-            spaces = GuardedWorkspaces(fill)
-            monkeypatch.setattr(ngp_hip, "workspace", spaces)
-            result = [r.detach().clone() for r in op()]
-            torch.cuda.synchronize()
-            spaces.check(at_least)
-            outs.append(result)
-        assert len(outs[0]) == len(outs[1]) > 0
-        for k, (a, b) in enumerate(zip(*outs)):
-            assert a.shape == b.shape and a.dtype == b.dtype and a.numel() > 0, k
-            assert torch.equal(a.contiguous().view(torch.uint8), b.contiguous().view(torch.uint8)), f"output {k} depends on what the workspace held"
-        return outs[0]
-    return run
+import _nav_cases as NC  # noqa: E402
+from _guard import GuardedWorkspaces, check_guarded, guarded, guarded_tensor  # noqa: E402,F401
 
 
 @pytest.fixture(scope="module")
@@ -209,3 +177,369 @@ def test_render_fused_cameras(guarded, dev, scene):
         return [out["image"], out["depth"].nan_to_num(), out["weights_sum"], out["stats"]]
     image, _, weights_sum, stats = guarded(op)
     assert image.shape == (2, 8, 8, 3) and float(weights_sum.max()) > 0.5 and int(stats[0]) > 100
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# the paths added since: one case each
+# ------------------------------------------------------------------------------------------------------------------------
+def default_field(dev, **kw):
+    """the default float32 field (ngp.field.NGPField) with the workload's table and nav weights: the field of the plan_epochs case"""
+    from ngp import workload as W
+    from ngp.field import NGPField
+    model = W.make_model(0)
+    sw, cw = W.nav_weights(0)
+    field = NGPField(bound=W.BOUND, **kw).to(dev)
+    with torch.no_grad():
+        field.encoder.embeddings.copy_(torch.from_numpy(model["embeddings"]))
+        for layer, w in zip(list(field.sigma_net) + list(field.color_net), sw + cw):
+            layer.weight.copy_(torch.from_numpy(w))
+    return field
+
+
+@pytest.fixture(scope="module")
+def nav_renderer(dev):
+    """the default float32 field behind a renderer that holds the workload's occupancy grid; frozen by the queries built on it"""
+    from ngp import workload as W
+    from ngp.render import NGPRenderer
+    ren = NGPRenderer(default_field(dev), bound=W.BOUND, cuda_ray=True, density_thresh=10.0).to(dev).eval()
+    ren.load_density_grid(W.density_grid())
+    return ren
+
+
+@pytest.fixture(scope="module")
+def train_field(dev):
+    return default_field(dev, fused_training=True).train()
+
+
+def frame_rays(W, n, dev):
+    """n rays from the middle rows of a 16 x 16 view of the ring from orbit pose 1 (pixels 95 ..: a third of them cross occupied cells within 8 steps)"""
+    o, d = W.get_rays(W.orbit_pose(1), W.intrinsics(16, 16), 16, 16)
+    return t(o[95:95 + n], dev), t(d[95:95 + n], dev)
+
+
+def test_inference_march(guarded, dev):
+    """65 alive rays: two 64-ray workgroups (RM_RAY_BLOCK), the last with one ray; 4 steps a ray, one cascade of 16^3.  The workspace is the coarse map
+    (k_rm_build_coarse writes its C H^3 / 2048 = 2 words) and the occupied box behind it (k_rm_occupied_box writes its 7 floats), both before k_march_rays
+    stages and reads them; the size function reserves the largest map (48 KiB), so the box sits 8 bytes into the buffer and the rest is never touched"""
+    import raymarching
+    from _util import camera_rays
+    N, n_step, C, H, bound = 65, 4, 1, 16, 1.0
+    o, d = camera_rays(8, radius=2.2, seed=3)
+    o, d = t(o[:N], dev), t(d[:N], dev)
+    bits = t(np.random.default_rng(5).integers(0, 256, C * H ** 3 // 8, dtype=np.uint8), dev)
+    nears, fars = raymarching.near_far_from_aabb(o, d, t(np.array([-bound] * 3 + [bound] * 3, np.float32), dev), 0.05)
+    alive = torch.arange(N, dtype=torch.int32, device=dev)
+
+    def op():
+        return list(raymarching.march_rays(N, n_step, alive, nears.clone(), o, d, bound, bits, C, H, nears, fars, 128, False, 0.0, 16))
+    x, dirs, deltas = guarded(op)
+    assert x.shape[0] == 384 and int((deltas[:, 0] > 0).sum()) > 64 and bool((deltas[N * n_step:] == 0).all())
+
+
+def test_density_sigma(guarded, dev, scene):
+    """33 points under autocast: two 32-row tiles of the density net, the second with one row.  The workspace holds the 16 levels' encoded features of
+    Mp = 64 rows: k_ft_encode_levels writes every row of every level (rows past M as zeros) before k_field_density_mlp reads them"""
+    W, field = scene
+    x = ((torch.rand(33, 3, generator=torch.Generator().manual_seed(8)) * 2 - 1) * W.BOUND).to(dev)
+
+    def op():
+        with torch.autocast("cuda", dtype=torch.float16):
+            return [field.density_sigma(x)]
+    sig, = guarded(op)
+    assert sig.shape == (33,) and bool(torch.isfinite(sig).all()) and float(sig.max()) > 2 * float(sig.min()) > 0
+
+
+@pytest.mark.parametrize("shape, B", [((32, 16, 64, 2, "relu"), 33), ((48, 3, 128, 3, "softplus"), 37)], ids=["registers", "layers"])
+def test_ffmlp_autograd(guarded, dev, shape, B):
+    """forward and backward of FFMLP with input gradients.  registers: the 32-64-64-16 net at B = 33, which the module pads to 64 rows (two 32-row tiles
+    of the backward); layers: FFMLP(48, 3, 128, 3, softplus) at B = 37, padded to 64 (four 16-row tiles of k_fg_layer, two 32-sample steps of
+    k_fg_wgrad).  The workspace: partial sums [rows][nw] | transposed weights | 256 spare bytes.  The transposes (k_fg_transpose / the register
+    kernels' own) are written before the activation-gradient launches read them; every launched workgroup column of the weight-gradient kernels stores
+    its whole row of partial sums, and the summing launch reads exactly the rows that were launched"""
+    from ffmlp import FFMLP
+    in_dim, out_dim, hidden, layers, act = shape
+    net = FFMLP(in_dim, out_dim, hidden, layers, activation=act).to(dev).train()
+    g = torch.Generator().manual_seed(B)
+    x0 = (torch.rand(B, in_dim, generator=g) - 0.5).to(dev)
+    go = torch.randn(B, out_dim, generator=g).to(dev)
+
+    def op():
+        net.weights.grad = None
+        x = x0.clone().requires_grad_(True)
+        with torch.autocast("cuda", dtype=torch.float16):
+            y = net(x)
+        (y.float() * go).sum().backward()
+        return [y, x.grad, net.weights.grad]
+    y, gx, gw = guarded(op)
+    assert y.shape == (B, out_dim) and gx.shape == (B, in_dim) and float(gx.abs().max()) > 0 and float(gw.abs().max()) > 0
+    assert all(bool(torch.isfinite(v.float()).all()) for v in (y, gx, gw))
+
+
+@pytest.mark.parametrize("M, reproducible", [(33, False), (257, False), (257, True)], ids=["33", "257", "257-reproducible"])
+def test_default_field_training_step(guarded, dev, train_field, M, reproducible):
+    """the float32 field's fused forward and backward with table and weight gradients.  33: one 256-sample chunk, partial; 257: two chunks (NT_CHUNK; the
+    partial sums are per workgroup of 256 samples), the second with one sample.  `saved`: k_nt_forward writes the 32 features of every live sample,
+    k_nt_backward reads them (rows past M are read at row M - 1).  The backward's workspace: every workgroup's four waves store all five accumulator
+    tiles before k_nt_reduce adds them.  The prepared weights: k_nav_transpose fills all five matrices before the forward reads them.  reproducible: the
+    float32 binned scatter draws its own workspace inside the step"""
+    field = train_field
+    field.reproducible = reproducible
+    g = torch.Generator().manual_seed(M)
+    x = ((torch.rand(M, 3, generator=g) * 2 - 1) * field.bound).to(dev)
+    d = torch.nn.functional.normalize(torch.randn(M, 3, generator=g), dim=-1).to(dev)
+    gs, gc = torch.randn(M, generator=g).to(dev), torch.randn(M, 3, generator=g).to(dev)
+    weights = [l.weight for l in list(field.sigma_net) + list(field.color_net)]
+
+    def op():
+        field._native, field._native_ok = None, {}            # the prepared weights are drawn again, through the guard
+        for p in field.parameters():
+            p.grad = None
+        sig, rgb = field(x, d)
+        ((sig * gs).sum() + (rgb * gc).sum()).backward()
+        table = field.encoder.embeddings.grad
+        assert bool(torch.isfinite(table).all()) and float(table.abs().max()) > 0
+        # the table gradient is compared bit for bit only where it is summed in a fixed order: the default scatter adds with float atomics, whose order
+        # (and so whose last bit, where three samples meet in one entry) changes from run to run whatever the workspace held
+        return [sig, rgb] + [w.grad for w in weights] + ([table] if binned else [])
+    from gridencoder import grid as G
+    binned = reproducible or G.BINNED_SCATTER_F32
+    out = guarded(op, at_least=4 if binned else 3)            # prepared weights, kept features, partial sums (, the scatter's workspace)
+    assert all(bool(torch.isfinite(o).all()) for o in out) and all(float(o.abs().max()) > 0 for o in out[4:7])        # the colour net's three gradients
+    field.reproducible = False
+
+
+def test_default_frame(guarded, dev, nav_renderer):
+    """the float32 frame (csrc/nav_frame.hip): render_fused on 65 rays (a wave draws 64 rays from the queue at a time: two draws, the second of one ray)
+    and render_fused_camera at 8 x 8 (one 8 x 8 tile).  The workspace is the 64-word header: hipMemsetAsync clears it in-stream before the kernel's first
+    atomicAdd on the queue head (word 0)"""
+    from ngp import workload as W
+    ren = nav_renderer
+    o, d = frame_rays(W, 65, dev)
+
+    def op():
+        ren.__dict__.pop("_default_frame_holder", None)       # the prepared weights are drawn again, through the guard
+        a = ren.render_fused(o[None], d[None], bg_color=(0.2, 0.4, 0.9))
+        b = ren.render_fused_camera(W.orbit_pose(1), W.intrinsics(8, 8), 8, 8, bg_color=(0.2, 0.4, 0.9))
+        return [a["image"], a["depth"].nan_to_num(), a["weights_sum"], a["stats"], b["image"], b["depth"].nan_to_num(), b["weights_sum"], b["stats"]]
+    out = guarded(op, at_least=3)                             # the prepared weights and a header per frame
+    assert out[0].shape == (1, 65, 3) and out[4].shape == (8, 8, 3) and int(out[3][0]) > 0 and int(out[7][0]) > 32
+    assert float(out[2].max()) > 0.01 and float(out[6].max()) > 0.01
+
+
+def test_half_frame_single_routes(guarded, dev, scene):
+    """the half frame kernel's single-frame entry points: render_fused on 65 rays with image_width 0 (no tiles: the band queues hand out ray indices; two
+    waves' worth, the second of one ray) and render_fused_camera at 8 x 8 (one tile, so the tile order runs: k_tile_cost writes cost[0], k_tile_sort reads
+    it and writes perm[0], the frame kernel reads perm only inside a band's own tile range).  Header: cleared by hipMemsetAsync before anything reads it;
+    coarse map and occupied extent: k_build_coarse writes all C H^3 / 2048 words before k_tile_cost and the frame kernel read them"""
+    from ngp.render import NGPRenderer
+    W, field = scene
+    ren = NGPRenderer(field, bound=W.BOUND, cuda_ray=True, density_thresh=10.0).to(dev).eval()
+    ren.load_density_grid(W.density_grid())
+    o, d = frame_rays(W, 65, dev)
+
+    def op():
+        a = ren.render_fused(o[None], d[None], bg_color=(0.2, 0.4, 0.9), image_width=0)
+        b = ren.render_fused_camera(W.orbit_pose(1), W.intrinsics(8, 8), 8, 8, bg_color=(0.2, 0.4, 0.9))
+        return [a["image"], a["depth"].nan_to_num(), a["weights_sum"], a["stats"], b["image"], b["depth"].nan_to_num(), b["weights_sum"], b["stats"]]
+    out = guarded(op, at_least=2)
+    assert out[0].shape == (1, 65, 3) and out[4].shape == (8, 8, 3) and int(out[3][0]) > 0 and int(out[7][0]) > 32
+    assert float(out[2].max()) > 0.01 and float(out[6].max()) > 0.01
+
+
+def test_nav_run(guarded, dev, nav_renderer):
+    """render_fn and render_fn_occupied on 65 rays of 8 steps with gradients to the rays (one workgroup, or one wave, per ray: T = 8 is a partial chunk of
+    the 256 / 64 samples a pass takes).  `saved`: k_nav_run_fwd stores all 27 words of every live sample, k_nav_run_bwd reads only those (lanes past T read
+    sample T - 1).  The occupied record adds the counts [N] and lists [N][T]: lane 0 of every ray stores its count, the forward stores list entries
+    [0, count), and the backward clamps count to T and reads list and records [0, count) only; a ray with count 0 reads nothing.  The prepared weights:
+    k_nav_transpose fills them before the first query"""
+    from ngp import nav
+    from ngp import workload as W
+    o0, d0 = frame_rays(W, 65, dev)
+    gi = torch.randn(65, 3, generator=torch.Generator().manual_seed(65)).to(dev)
+
+    def op():
+        queries = nav.NativeNavQueries(nav_renderer, W.intrinsics(16, 16), 16, 16, num_steps=8)
+        out = []
+        for occupied in (False, True):
+            o, d = o0.clone().requires_grad_(True), d0.clone().requires_grad_(True)
+            if occupied:
+                counts = torch.zeros(65, dtype=torch.int32, device=dev)
+                image, depth, ws = queries.render_fn_occupied(o, d, counts)
+                out.append(counts)
+            else:
+                res = queries.render_fn(o[None], d[None])
+                image, depth = res["image"][0], res["depth"][0]
+            ((image * gi).sum() + depth.sum()).backward()
+            out += [image, depth, o.grad, d.grad]
+        return out
+    out = guarded(op, at_least=3)                             # the prepared weights, the dense record, the occupied record
+    counts = out[4]
+    assert all(bool(torch.isfinite(v.float()).all()) for v in out) and float(out[2].abs().max()) > 0 and float(out[7].abs().max()) > 0
+    assert 0 < int(counts.sum()) < 65 * 8 and not torch.equal(out[0], out[5])
+
+
+def filter_setting(dev, B, n_iter, seed):
+    """the golden prior of tests/golden/callers_nav.npz, a random 16 x 16 target and n_iter batches of B pixels (drawn with replacement: B may exceed 256)"""
+    g = NC.gold()
+    rng = np.random.default_rng(seed)
+    target = torch.from_numpy(rng.uniform(0, 1, (16, 16, 3)).astype(np.float32)).to(dev)
+    batches = torch.from_numpy(rng.integers(0, 16, (n_iter, B, 2)).astype(np.int32)).to(dev)
+    return dict(start=torch.from_numpy(g["mf_start"]).to(dev), sig=torch.from_numpy(g["mf_sig"]).to(dev), target=target, batches=batches)
+
+
+def make_filter(queries, B, n_iter, **kw):
+    from ngp import nav
+    return nav.NativePoseFilter({"batch_size": B, "lrate": 1e-3, "N_iter": n_iter, "sig0": torch.eye(12), "Q": torch.eye(12), "kernel_size": 3, "dil_iter": 1},
+                                queries, **kw)
+
+
+def filter_queries(nav_renderer):
+    from ngp import nav
+    return nav.NativeNavQueries(nav_renderer, NC.gold()["mf_intrinsics"], 16, 16, num_steps=8)
+
+
+@pytest.mark.parametrize("B", [65, 257])
+@pytest.mark.parametrize("sampling", ["dense", "occupied"])
+def test_pose_filter_loop(guarded, dev, nav_renderer, sampling, B):
+    """estimate_relative_pose, 2 iterations of B rays of 8 steps on a 16 x 16 image.  B = 65: 65 ray workgroups of the run kernels, one 256-ray block of
+    the filter's own kernels; B = 257: two blocks of k_filter_rays / k_filter_loss (NF_THREADS = 256), the second with one ray, and two loss partials.
+    Per iteration, in stream order: k_filter_rays writes rays_o, rays_d, nears, fars [B]; the run forward reads them and writes image, depth,
+    weights_sum and the record; k_filter_loss reads image and writes grad_image [B] and the partials; the run backward reads grad_image and the
+    record (test_nav_run) and writes grad_rays_o, grad_rays_d [B]; k_filter_step reads those and the partials.  No piece is read before that
+    iteration wrote it, so nothing is carried from one iteration, or one call, to the next"""
+    s = filter_setting(dev, B, 2, 10 + B)
+
+    def op():
+        filt = make_filter(filter_queries(nav_renderer), B, 2, sampling=sampling)
+        final = filt.estimate_relative_pose(s["target"], s["start"], s["sig"], s["batches"])
+        return [final, filt.losses, filt.states, filt.grads]
+    final, losses, states, grads = guarded(op, at_least=2)    # the prepared weights and the loop's workspace
+    assert all(bool(torch.isfinite(v).all()) for v in (final, losses, states, grads)) and float(grads.abs().max()) > 0
+    assert torch.equal(states[0], s["start"] + 1e-6) and not torch.equal(final, states[1]) and float(losses.min()) > 0
+
+
+@pytest.mark.parametrize("B", [33, 257])
+def test_pose_filter_multi(guarded, dev, nav_renderer, B):
+    """estimate_relative_pose_multi, K = 3 hypotheses of B rays, 2 iterations and the measurement pass.  Every per-ray piece holds K B rays, hypothesis k
+    in [k B, (k + 1) B); B = 257 gives each hypothesis two loss partials, the second of one ray (K slices of ceil(B / 256)).  The order of writes and
+    reads is the single loop's (test_pose_filter_loop) with the multi kernels' grid (blocks, K)"""
+    s = filter_setting(dev, B, 2, 20 + B)
+    offsets = torch.zeros(3, 12)
+    offsets[1, :3], offsets[2, 6:9] = torch.tensor([0.05, -0.04, 0.03]), torch.tensor([0.04, 0.0, -0.03])
+
+    def op():
+        filt = make_filter(filter_queries(nav_renderer), B, 2)
+        best = filt.estimate_relative_pose_multi(s["target"], s["start"], s["sig"], s["batches"], offsets)
+        m = filt.multi
+        return [best, m["states"], m["final_losses"], m["index"], m["losses"], m["states_hist"], m["grads"]]
+    out = guarded(op, at_least=2)
+    assert all(bool(torch.isfinite(v.float()).all()) for v in out) and float(out[6].abs().max()) > 0
+    assert len({tuple(r.tolist()) for r in out[4][0].reshape(3, 1)}) == 3          # three different objectives: no slice was read for another
+
+
+def feature_image(dev, which=0):
+    """16 x 16 grey images with a few bright squares; the host detector (ngp_features_detect_host) finds 3 keypoints in the first and 1 in the second,
+    and the 3 x 3 dilation turns them into 27 and 9 pixels"""
+    im = np.full((16, 16, 3), 0.1 if which == 0 else 0.2, np.float32)
+    squares = [(3, 3, 2, 0.9), (9, 5, 3, 0.8), (5, 10, 2, 1.0), (11, 11, 2, 0.7)] if which == 0 else [(6, 6, 3, 0.95), (2, 11, 2, 0.8)]
+    for r, c, n, v in squares:
+        im[r:r + n, c:c + n] = v
+    return torch.from_numpy(im).to(dev)
+
+
+def test_feature_front(guarded, dev, nav_renderer):
+    """detect -> interest_regions -> draw_batches_native on a 16 x 16 image (the smallest the detector takes: three octaves of 32, 16 and 8 pixels a side,
+    one 1024-pixel chunk of the list kernels).  Pyramid: k_feat_blur<1> writes level 0 of octave 0, each k_feat_blur<0> level i from level i - 1 and
+    level 0 of the next octave from level `layers`, all before that octave's k_feat_extrema reads them.  The dilated mask is cleared in-stream
+    (hipMemsetAsync) before k_feat_stamp; k_feat_count writes the chunk's count and its 16 bitmap words before k_feat_list_write reads them"""
+    image = feature_image(dev)
+
+    def op():
+        filt = make_filter(filter_queries(nav_renderer), 16, 2)
+        mask = filt.detect(image)
+        regions = filt.interest_regions(image)
+        return [mask, regions, filt.draw_batches_native(regions, 2, 7)]
+    mask, regions, batches = guarded(op)                      # the detector's workspace (the front asks nothing of the field)
+    M = regions.shape[0]
+    assert int(mask.sum()) >= 1 and 16 <= M < 256 and batches.shape == (2, 16, 2)     # keypoints were found; M >= the batch size, not the whole image
+    pixels = {tuple(p) for p in regions.tolist()}
+    assert len(pixels) == M and all(tuple(p) in pixels for p in batches.reshape(-1, 2).tolist())
+    assert all(len({tuple(p) for p in b.tolist()}) == 16 for b in batches)         # drawn without replacement
+
+
+def test_plan_epochs_multi(guarded, dev, nav_renderer):
+    """run_epochs_multi, K = 2, on the plan_epochs case (R = 2 rows of states, three body points: 15 points a hypothesis, every piece of the workspace
+    shorter than its 256-byte slot).  Per epoch k_plan_kinematics (grid K) writes all K S B points, ngp_nav_density_value_jac writes sigma and jac of
+    all of them, k_plan_cost_step (grid K) reads its own slice"""
+    from ngp import nav
+    from ngp import workload as W
+    from oracle import nav_oracle as NO
+    cfg = {"T_final": 2., "steps": 4, "lr": 0.001, "epochs_init": 1, "epochs_update": 1, "fade_out_epoch": 0, "fade_out_sharpness": 10, "mass": 1.,
+           "I": torch.eye(3), "g": 10., "body": np.array([[-0.05, 0.05], [-0.05, 0.05], [-0.02, 0.02]]), "nbins": [3, 1, 1]}
+
+    def op():
+        queries = nav.NativeNavQueries(nav_renderer, (20.0, 20.0, 4.0, 4.0), 8, 8, num_steps=8)
+        plan = nav.NativePlanner(NO.state18([0.39, -0.67, 0.2]), NO.state18([-0.4, 0.55, 0.16]), cfg, queries)
+        assert plan.R == 2 and plan.robot_body.shape[0] == 3
+        states = (plan.states[None] + plan.draw_offsets(2, 0.05, generator=torch.Generator().manual_seed(1))).contiguous()
+        accel = plan.initial_accel[None].repeat(2, 1).contiguous()
+        adam, losses, per_state = plan.new_adam_state_multi(2), torch.empty(1, 2, device=dev), torch.empty(2, 2, plan.S, device=dev)
+        plan.run_epochs_multi(states, accel, 0, 1, adam, losses=losses, per_state=per_state)
+        return [states, accel, adam, losses, per_state]
+    out = guarded(op, at_least=2)                             # the prepared weights and the planner's workspace
+    # (the two starts lie 0.05 apart and their costs of 1.2e5 came out equal in float32, so no difference between the rows is asserted: that row k is
+    #  the single run from start k is tests/test_gpu_plan_multi.py's business; here the epoch ran -- positive costs, gradients and a step count)
+    assert all(bool(torch.isfinite(o).all()) for o in out) and float(out[3].min()) > 0 and float(out[2].abs().max()) > 0
+
+
+def test_mse_head_workspace(dev):
+    """the loss heads' workspace (ticket word | one partial sum per workgroup) is zeroed by its owner once and never again: three launches on one
+    guarded buffer of zeros, 4097 elements (two workgroups of TH_SLICE = 4096, the second with one element).  After each: guards intact, the ticket
+    zero again (the last workgroup puts it back), the same loss bits"""
+    import ngp_hip
+    L = ngp_hip.lib()
+    n = 4097
+    g = torch.Generator().manual_seed(n)
+    pred, target = torch.rand(n, generator=g).to(dev), torch.rand(n, generator=g).to(dev)
+    ws = guarded_tensor(int(L.ngp_mse_head_workspace()), torch.uint8, dev, 0xAB)
+    ws.zero_()
+    seen = []
+    for _ in range(3):
+        loss, unit = guarded_tensor(2, torch.float32, dev, 0xFF), guarded_tensor(n, torch.float32, dev, 0xFF)
+        ngp_hip.check(L.ngp_mse_head_forward(ngp_hip.ptr(pred), ngp_hip.ptr(target), n, None, ngp_hip.ptr(loss), ngp_hip.ptr(unit), ngp_hip.ptr(ws),
+                                             ws.numel(), ngp_hip.stream()), "mse_head_forward")
+        torch.cuda.synchronize()
+        for name, buf in (("workspace", ws), ("loss", loss), ("grad_unit", unit)):
+            check_guarded(buf, name)
+        assert int(ws[:4].view(torch.int32)) == 0 and bool(torch.isfinite(unit).all())
+        seen.append(loss.clone())
+    assert 0.05 < float(seen[0][0]) < 0.5 and torch.equal(seen[0][0], seen[0][1])       # the mean of (u - v)^2 for uniform u, v is 1 / 6; no scale: both words
+    assert all(torch.equal(seen[0].view(torch.int32), s.view(torch.int32)) for s in seen[1:])
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# the checker itself: a byte the test writes into a guard is reported, front and back
+# ------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("fill", [0xAB, 0x00])
+def test_the_checks_see_one_byte_in_either_guard(dev, fill):
+    spaces = GuardedWorkspaces(fill)
+    ws = spaces(100, dev)
+    assert ws.numel() == 100 and ws.data_ptr() % 256 == 0
+    spaces.check(1)
+    with pytest.raises(AssertionError, match="expected 2"):
+        spaces.check(2)
+    for at, where in ((255, "in front of"), (256 + 100, "behind")):
+        spaces.buffers[0][at] = fill ^ 1                     # a torch write to the test's own buffer: the last byte before, the first byte after
+        with pytest.raises(AssertionError, match=where):
+            spaces.check(1)
+        spaces.buffers[0][at] = fill
+    spaces.check(1)
+    x = guarded_tensor((7, 3), torch.float16, dev, fill)
+    assert x.shape == (7, 3) and x.is_contiguous() and x.data_ptr() % 256 == 0 and x.guard_buffer.numel() == 42 + 512
+    check_guarded(x)
+    for at, where in ((255, "in front of"), (256 + 42, "behind")):
+        x.guard_buffer[at] = fill ^ 1
+        with pytest.raises(AssertionError, match=where):
+            check_guarded(x, "x")
+        x.guard_buffer[at] = fill
+    check_guarded(x)
