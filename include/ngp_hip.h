@@ -577,6 +577,47 @@ int ngp_nav_run_occ_backward(const ngp_nav_field_t* field_host, const void* prep
                              const float* bg_color3_host, const float* grad_image, const float* grad_depth, const float* grad_weights_sum,
                              const void* saved, size_t saved_bytes, float* grad_rays_o, float* grad_rays_d, void* stream);
 
+/* Resampled run: NeRFRenderer.run with upsample_steps > 0, perturb = False, deterministic sample_pdf (nerf/renderer.py:172-204, :12-46; DESIGN.md 3.5
+ * "Resampled run").  Nc = num_steps >= 3 coarse samples, Nf = upsample_steps >= 1 new ones, T = Nc + Nf <= 4096.  All arithmetic float32, one rounding
+ * per operation, except where stated.
+ *   coarse pass   positions, deltas (last = (far - near) / Nc), sigma and w_i = alpha_i prod_{k<i} (1 - alpha_k + 1e-15) are ngp_nav_run_forward's at
+ *                 num_steps = Nc; no colour net, nothing saved.  z_i = near + (far - near) * linspace(0, 1, Nc)[i].
+ *   bins, pdf     bins_i = z_i + 0.5 * (z_{i+1} - z_i), i < Nc - 1 (Tb = Nc - 1 of them); the pdf is over w[1 : Nc - 1] (Tb - 1 weights).
+ *   sample_pdf    v_k = w_k + 1e-5 (float32).  THE TWO SUMS ARE TAKEN IN 64-BIT FIXED POINT: q_k = (int64) rint(v_k * 2^40) (exact for
+ *                 2^-17 <= v_k; a v_k that is negative or NaN counts as 0, one above 1024 as 1024), S = sum q_k, P_k = sum_{m<k} q_m, both exact
+ *                 and so independent of order; cdf_k = (float) ((double) P_k / (double) S), k = 0 .. Tb - 1: cdf_0 = 0, cdf_{Tb-1} = 1 (S = 0: all 0).
+ *                 u_j = linspace(s, e, n)[j] with s = (float) (0.5 / n), e = (float) (1 - 0.5 / n) (both formed in double), in ATen's rule:
+ *                 step = (e - s) / (float) (n - 1); j < n / 2: fma(step, j, s), else fma(-step, n - 1 - j, e); n = 1: s.
+ *                 hi = #{k : cdf_k <= u} (searchsorted, right = True), lo = max(hi - 1, 0), hi = min(hi, Tb - 1); denom = cdf_hi - cdf_lo, 1 where < 1e-5;
+ *                 z_new = min(bins_lo + ((u - cdf_lo) / denom) * (bins_hi - bins_lo), bins_hi).  The min differs from the reference only where its own
+ *                 float32 sum steps one ulp past the bin's upper edge; with it z_new is non-decreasing in j (for non-decreasing u) and inside the bins.
+ *   merge         z [N,T]: the stable sort of cat(z coarse, z_new): coarse i at i + #{j : z_new_j < z_i}, new j at Nc + j - #{i : z_i > z_new_j}
+ *                 = j + #{i : z_i <= z_new_j}; on equal depths coarse first, new samples in j order.  z is a constant: no gradient through it.
+ *   final pass    ngp_nav_run_at_forward / _backward over z with dist_steps = Nc: ngp_nav_run_forward's arithmetic with z_i read from the list,
+ *                 deltas z_{i+1} - z_i, the last (far - near) / dist_steps; the record is ngp_nav_run_saved_bytes(N, T).
+ * A ray with near == far gets T copies of near, zero weights, the background, weights_sum = depth = 0 and zero gradients.  No atomics: two runs give
+ * the same bits and a ray's outputs depend on nothing but the ray.
+ *
+ * ngp_sample_pdf: the sample_pdf step alone on caller-given rows: bins [N,Tb] (non-decreasing per row), weights [N,Tb-1], 2 <= Tb <= 4096, n >= 1;
+ * u: NULL (the deterministic linspace above) or [N,n] caller-given uniforms; out [N,n]. */
+int ngp_sample_pdf(const float* bins, const float* weights, uint32_t N, uint32_t Tb, const float* u, uint32_t n, float* out, void* stream);
+/* coarse pass + sample_pdf + merge, one workgroup per ray: z [N, num_steps + upsample_steps]; coarse_weights [N,num_steps] or NULL.
+ * NGP_EINVAL before anything is queued: num_steps < 3, upsample_steps = 0, num_steps + upsample_steps > 4096, a null pointer (z included), and
+ * whatever ngp_nav_run_forward refuses of the field. */
+int ngp_nav_run_resample(const ngp_nav_field_t* field_host, const void* prepared, const float* rays_o, const float* rays_d, const float* nears,
+                         const float* fars, uint32_t N, uint32_t num_steps, uint32_t upsample_steps, const float* aabb_host, float* z,
+                         float* coarse_weights, void* stream);
+/* ngp_nav_run_forward / _backward over an explicit depth list: their arguments, with T (the length of each ray's list, 1 .. 4096) where they take
+ * num_steps, then z [N,T] (non-decreasing per ray; NGP_EINVAL if null) and dist_steps >= 1 (the last delta is (far - near) / dist_steps), then the stream.
+ * saved: ngp_nav_run_saved_bytes(N, T) bytes, same record layout. */
+int ngp_nav_run_at_forward(const ngp_nav_field_t* field_host, const void* prepared, const float* rays_o, const float* rays_d, const float* nears,
+                           const float* fars, uint32_t N, uint32_t T, const float* aabb_host, const float* bg_color3_host, float* image,
+                           float* depth, float* weights_sum, void* saved, size_t saved_bytes, const float* z, uint32_t dist_steps, void* stream);
+int ngp_nav_run_at_backward(const ngp_nav_field_t* field_host, const void* prepared, const float* rays_o, const float* rays_d, const float* nears,
+                            const float* fars, uint32_t N, uint32_t T, const float* aabb_host, const float* bg_color3_host,
+                            const float* grad_image, const float* grad_depth, const float* grad_weights_sum, const void* saved, size_t saved_bytes,
+                            float* grad_rays_o, float* grad_rays_d, const float* z, uint32_t dist_steps, void* stream);
+
 /* Training forward and backward of the same field (NeRFNetwork.forward, nerf/network.py:95-123, float32; csrc/nav_train.hip).
  * forward: xyzs, dirs [M,3] -> sigmas [M] = exp(h0) (field_host->density_scale is NOT applied: the renderer does that), rgbs [M,3] after the sigmoid;
  *   a sample outside [-bound, bound]^3 encodes to zeros.  saved: ngp_nav_field_train_saved_bytes(M) bytes (the 32 encoded features, 128 B per sample).
@@ -859,6 +900,23 @@ int ngp_filter_iterations_occ(const ngp_nav_field_t* field_host, const void* pre
 int ngp_filter_hessian_occ(const ngp_nav_field_t* field_host, const void* prepared, const ngp_filter_cfg_t* cfg_host, const ngp_occ_grid_t* grid_host,
                            const float* state, const float* target, const int32_t* batch, float* hessian, float* grad, float* loss, float* dLdP,
                            void* workspace, size_t workspace_bytes, void* stream);
+
+/* The loop and the Hessian over the resampled run (DESIGN.md 3.5 "Resampled run"): opt-in, the entry points above keep their code path.  The measurement
+ * pass is rays, ngp_nav_run_resample, ngp_nav_run_at_forward, loss, ngp_nav_run_at_backward; with the step that is six launches per iteration, no
+ * synchronisation, no host read.  cfg_host->num_steps = Nc, upsample_steps = Nf, T = Nc + Nf.
+ * ngp_filter_iterations_multi's arguments, then upsample_steps and z [K B, T] (device, caller-provided, overwritten every iteration), then the stream.
+ * workspace: ngp_filter_multi_workspace(K, B, T) bytes (the record is ngp_nav_run_saved_bytes(K B, T)).  Row k of every output is bit for bit the
+ * K = 1 run from states[k].  NGP_EINVAL: num_steps < 3, upsample_steps = 0, T > 4096, a null z, and what ngp_filter_iterations_multi refuses;
+ * NGP_EWORKSPACE: a null or short workspace. */
+int ngp_filter_iterations_res(const ngp_nav_field_t* field_host, const void* prepared, const ngp_filter_cfg_t* cfg_host, uint32_t K, float* states,
+                              float* adam_states, const float* target, const int32_t* batches, uint32_t first_iter, uint32_t n_iter, int update,
+                              float* losses, float* states_out, float* grads_out, void* workspace, size_t workspace_bytes,
+                              uint32_t upsample_steps, float* z, void* stream);
+/* ngp_filter_hessian's arguments, then upsample_steps and z [B, T], then the stream; gradient and loss are bit for bit what an update = 0 iteration of
+ * ngp_filter_iterations_res (K = 1) writes.  workspace: ngp_filter_workspace(B, T) bytes. */
+int ngp_filter_hessian_res(const ngp_nav_field_t* field_host, const void* prepared, const ngp_filter_cfg_t* cfg_host, const float* state,
+                           const float* target, const int32_t* batch, float* hessian, float* grad, float* loss, float* dLdP, void* workspace,
+                           size_t workspace_bytes, uint32_t upsample_steps, float* z, void* stream);
 
 /* The front of the time step: the sensor image's interest regions and the loop's batches (Estimator.find_POI, the dilation, coords[mask] and the draw,
  * nav/estimator_helpers.py:181-204, 229-230; csrc/nav_features.hip, csrc/ngp_features.h, DESIGN.md §3.5 "Native interest regions").

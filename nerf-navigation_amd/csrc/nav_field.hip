@@ -17,6 +17,8 @@
 //                              to d L / d xyz, reduced into d L / d rays_o and d L / d rays_d.
 //   k_nav_run_occ_fwd / _bwd   the same run with the occupancy grid consulted (sigma = 0 where the bit is clear), one WAVE per ray over the compacted
 //                              list of its occupied samples: the pose filter's opt-in route (the section before "host side" below)
+//   k_nav_resample, k_sample_pdf, k_nav_run_fwd<true> / _bwd<true>   the run with upsample_steps > 0: the coarse pass, sample_pdf's inverse CDF and the depth-ordered
+//                              merge in one launch, then the run kernels over that explicit depth list ("The resampled run" below)
 // float32 FMA throughput is the same on the VALU and on the f32 MFMA of this chip, and the batch is small (10 k - 524 k points), so
 // the matrix cores would buy nothing here; what the fusion removes is launches and the [M, 64] round trips through HBM.
 //
@@ -204,6 +206,9 @@ struct nav_run {
     float aabb[6];
     float bg[3];
 };
+// the explicit depth list [N, T] of the AT instantiations of the run kernels and their sample_dist = (far - near) / dist.  The LAST kernel argument, so that
+// the linspace instantiations, which never read it, keep the argument offsets and the code they had
+struct nav_at { const float* z; uint32_t dist; };
 
 // torch.linspace(0, 1, T)[i] in float32 as ATen's GPU kernel produces it (RangeFactories.cu: start + step * i for the first half,
 // end - step * (T - 1 - i) for the second, compiled with contraction: ONE rounding).  Matching its bits matters more than it looks: a
@@ -225,14 +230,22 @@ __device__ __forceinline__ float nv_clip_pass(float x, float lo, float hi) {
     return a * b;
 }
 
+// AT: the depths come from the ray's row of the depth list (`zrow`, T entries) instead of the linspace lattice, and the last delta is (far - near) / dist
+template <bool AT = false>
 __device__ __forceinline__ nv_sample nv_sample_at(const nav_run& R, uint32_t i, float near, float far, float ox, float oy, float oz,
-                                                  float dx, float dy, float dz) {
+                                                  float dx, float dy, float dz, const float* __restrict__ zrow = nullptr, uint32_t dist = 0) {
     nv_sample s;
     const float span = far - near;
-    s.lin = nv_lin(i, R.T);
-    s.z = near + span * s.lin;                                           // :147-148
-    const float zn = (i + 1 < R.T) ? near + span * nv_lin(i + 1, R.T) : 0.0f;
-    s.znext_minus_z = (i + 1 < R.T) ? zn - s.z : span / (float)R.T;      // deltas, last = sample_dist (:206-207, :151)
+    if (AT) {
+        s.lin = 0.0f;
+        s.z = zrow[i];                                                   // the merged list (:196-197)
+        s.znext_minus_z = (i + 1 < R.T) ? zrow[i + 1] - s.z : span / (float)dist;        // :206-207 with :153's sample_dist
+    } else {
+        s.lin = nv_lin(i, R.T);
+        s.z = near + span * s.lin;                                       // :147-148
+        const float zn = (i + 1 < R.T) ? near + span * nv_lin(i + 1, R.T) : 0.0f;
+        s.znext_minus_z = (i + 1 < R.T) ? zn - s.z : span / (float)R.T;  // deltas, last = sample_dist (:206-207, :151)
+    }
     const float x = ox + dx * s.z, y = oy + dy * s.z, z = oz + dz * s.z; // :158
     s.px = fminf(fmaxf(x, R.aabb[0]), R.aabb[3]);                        // :159
     s.py = fminf(fmaxf(y, R.aabb[1]), R.aabb[4]);
@@ -286,8 +299,9 @@ static constexpr uint32_t NV_REC_WORDS = 27;
 // 2^-25, which for an opaque sample (ex = 1e-4) is 3e-4 of d alpha / d sigma = delta scale ex, and that sample is the one the ray's gradient hangs on
 enum { NV_R_OUT = 0, NV_R_RELU = 16, NV_R_EX = 18, NV_R_TR = 19, NV_R_RGB = 20, NV_R_MA = 23, NV_R_MB = 25 };
 
+template <bool AT>
 __global__ __launch_bounds__(NV_BLOCK) void k_nav_run_fwd(nav_params P, nav_run R, float* __restrict__ image, float* __restrict__ depth,
-                                                          float* __restrict__ weights_sum, uint32_t* __restrict__ save) {
+                                                          float* __restrict__ weights_sum, uint32_t* __restrict__ save, nav_at Z) {
     extern __shared__ float nv_smem[];
     float* lds4 = nv_smem;                                              // 16 floats of scan scratch
     float* col = nv_smem + 16 + threadIdx.x;                            // this lane's column of the [64][256] scratch
@@ -296,11 +310,12 @@ __global__ __launch_bounds__(NV_BLOCK) void k_nav_run_fwd(nav_params P, nav_run 
     const float ox = R.rays_o[3ull * n], oy = R.rays_o[3ull * n + 1], oz = R.rays_o[3ull * n + 2];
     const float dx = R.rays_d[3ull * n], dy = R.rays_d[3ull * n + 1], dz = R.rays_d[3ull * n + 2];
     const float near = R.nears[n], far = R.fars[n], span = far - near;
+    const float* zrow = AT ? Z.z + (size_t)n * R.T : nullptr;
     float carry = 1.0f, acc_w = 0.0f, acc_d = 0.0f, acc_r = 0.0f, acc_g = 0.0f, acc_b = 0.0f;
     for (uint32_t c0 = 0; c0 < R.T; c0 += NV_BLOCK) {
         const uint32_t i = c0 + threadIdx.x;
         const bool live = i < R.T;
-        const nv_sample s = nv_sample_at(R, live ? i : R.T - 1, near, far, ox, oy, oz, dx, dy, dz);
+        const nv_sample s = nv_sample_at<AT>(R, live ? i : R.T - 1, near, far, ox, oy, oz, dx, dy, dz, zrow, Z.dist);
         float x0, x1, x2;
         const bool inside = nv_normalise(P, s.px, s.py, s.pz, x0, x1, x2);
         float out[16];
@@ -374,9 +389,10 @@ __device__ __forceinline__ void nv_color_backward_saved(const nav_params& P, flo
     gdx += sx; gdy += sy; gdz += sz;
 }
 
+template <bool AT>
 __global__ __launch_bounds__(NV_BLOCK) void k_nav_run_bwd(nav_params P, nav_run R, const float* __restrict__ gimage, const float* __restrict__ gdepth,
                                                           const float* __restrict__ gws, const uint32_t* __restrict__ save,
-                                                          float* __restrict__ grays_o, float* __restrict__ grays_d) {
+                                                          float* __restrict__ grays_o, float* __restrict__ grays_d, nav_at Z) {
     extern __shared__ float nv_smem[];
     float* lds4 = nv_smem;
     float* col = nv_smem + 16 + threadIdx.x;
@@ -385,6 +401,7 @@ __global__ __launch_bounds__(NV_BLOCK) void k_nav_run_bwd(nav_params P, nav_run 
     const float ox = R.rays_o[3ull * n], oy = R.rays_o[3ull * n + 1], oz = R.rays_o[3ull * n + 2];
     const float dx = R.rays_d[3ull * n], dy = R.rays_d[3ull * n + 1], dz = R.rays_d[3ull * n + 2];
     const float near = R.nears[n], far = R.fars[n], span = far - near;
+    const float* zrow = AT ? Z.z + (size_t)n * R.T : nullptr;
     const float gi0 = gimage[3ull * n], gi1 = gimage[3ull * n + 1], gi2 = gimage[3ull * n + 2];
     const float gd = gdepth ? gdepth[n] : 0.0f, gw = gws ? gws[n] : 0.0f;
     const uint32_t nchunks = (R.T + NV_BLOCK - 1) / NV_BLOCK;
@@ -395,7 +412,7 @@ __global__ __launch_bounds__(NV_BLOCK) void k_nav_run_bwd(nav_params P, nav_run 
     for (uint32_t cc = nchunks; cc-- > 0;) {
         const uint32_t i = cc * NV_BLOCK + threadIdx.x;
         const bool live = i < R.T;
-        const nv_sample s = nv_sample_at(R, live ? i : R.T - 1, near, far, ox, oy, oz, dx, dy, dz);
+        const nv_sample s = nv_sample_at<AT>(R, live ? i : R.T - 1, near, far, ox, oy, oz, dx, dy, dz, zrow, Z.dist);
         const uint32_t* q = save + (size_t)n * R.T + (live ? i : R.T - 1);
         const float ex = live ? __uint_as_float(q[NV_R_EX * NT]) : 1.0f, Tr = live ? __uint_as_float(q[NV_R_TR * NT]) : 0.0f;
         const float alpha = 1.0f - ex;                                   // the forward's own alpha
@@ -669,6 +686,161 @@ __global__ __launch_bounds__(NO_W) void k_nav_run_occ_bwd(nav_params P, nav_run 
 }
 
 // ---------------------------------------------------------------------------
+// The resampled run (DESIGN.md §3.5 "Resampled run"; include/ngp_hip.h states the contract): NeRFRenderer.run's upsample_steps > 0 branch
+// (nerf/renderer.py:172-204) with sample_pdf's deterministic branch (:12-46).
+//
+//   k_nav_resample   one 256-thread workgroup per ray: k_nav_run_fwd's coarse pass without the colour net (the weights stay in LDS), the cdf of
+//                    w[1 : Nc - 1], one binary search per new sample, two rank searches for the merge; writes the merged depth list z [N, T]
+//   k_sample_pdf     the same device functions on caller-given bins / weights (and uniforms): the piece a host restatement reproduces bit for bit
+//   k_nav_run_fwd<true> / _bwd<true> then run over z (nv_sample_at<true>).
+//
+// The two sums of sample_pdf (the normaliser and the cumulative sum) are taken in 64-bit FIXED POINT, 2^-40 per unit: w + 1e-5 >= 2^-17 is a multiple
+// of 2^-40 in float32, so the conversion is exact, integer addition is associative, and any scan order gives the same cdf -- which a numpy restatement
+// reproduces from the same float32 weights.  cdf_k = (float)((double) P_k / (double) S): cdf_0 = 0 and the last entry is 1 exactly.
+// No atomics; the ray's outputs depend on nothing but the ray.
+// ---------------------------------------------------------------------------
+struct nv_pdf_u { float s, e, step; };                                   // linspace(0.5 / n, 1 - 0.5 / n, n): start, end, step (float32, ATen's rule)
+static constexpr size_t NV_PDF_SCAN_BYTES = 32;                          // one 64-bit total per wave
+
+static nv_pdf_u nv_pdf_u_of(uint32_t n) {
+    nv_pdf_u U;
+    U.s = (float)(0.5 / (double)n);
+    U.e = (float)(1.0 - 0.5 / (double)n);
+    U.step = n > 1 ? (U.e - U.s) / (float)(n - 1) : 0.0f;
+    return U;
+}
+
+__device__ __forceinline__ float nv_pdf_u_at(const nv_pdf_u& U, uint32_t j, uint32_t n) {
+    if (n < 2) return U.s;
+    return j < n / 2 ? __builtin_fmaf(U.step, (float)j, U.s) : __builtin_fmaf(-U.step, (float)(n - 1 - j), U.e);
+}
+
+__device__ __forceinline__ long long nv_pdf_fixed(float w) {
+    const float v = w + 1e-5f;                                           // :19
+    if (!(v >= 0.0f)) return 0;                                          // negative or NaN
+    return __float2ll_rn(fminf(v, 1024.0f) * 1099511627776.0f);          // 2^40: the product is exact
+}
+
+// cdf [Tb] (LDS) from the Tb - 1 weights w[] (LDS or global); `scan`: NV_PDF_SCAN_BYTES of LDS.  Every thread of the 256 calls it; thread t owns a
+// contiguous run of weights, the runs' totals are scanned by shuffles and the four wave totals through LDS.  Ends with a barrier: cdf is readable.
+__device__ __forceinline__ void nv_pdf_cdf(const float* __restrict__ w, uint32_t Tb, float* __restrict__ cdf, long long* __restrict__ scan) {
+    const uint32_t nb = Tb - 1, per = (nb + NV_BLOCK - 1) / NV_BLOCK;
+    const uint32_t k0 = min(threadIdx.x * per, nb), k1 = min(k0 + per, nb);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    long long own = 0;
+    for (uint32_t k = k0; k < k1; k++) own += nv_pdf_fixed(w[k]);
+    long long incl = own;
+    #pragma unroll
+    for (int off = 1; off < 64; off <<= 1) { const long long up = __shfl_up(incl, off, 64); if (lane >= off) incl += up; }
+    __syncthreads();
+    if (lane == 63) scan[wave] = incl;
+    __syncthreads();
+    long long base = 0, S = 0;
+    #pragma unroll
+    for (int v = 0; v < (int)(NV_BLOCK / 64); v++) { const long long t = scan[v]; if (v < wave) base += t; S += t; }
+    long long Pk = base + (incl - own);
+    if (threadIdx.x == 0) cdf[0] = 0.0f;
+    for (uint32_t k = k0; k < k1; k++) {
+        Pk += nv_pdf_fixed(w[k]);
+        cdf[k + 1] = S > 0 ? (float)((double)Pk / (double)S) : 0.0f;
+    }
+    __syncthreads();
+}
+
+// one new depth: searchsorted(cdf, u, right = True), the two clamps, the guarded quotient and the interpolation (:32-44); bins(k) = the k-th bin edge
+template <class Bins>
+__device__ __forceinline__ float nv_pdf_invert(const float* __restrict__ cdf, uint32_t Tb, float u, Bins bins) {
+    uint32_t a = 0, b = Tb;                                              // cdf[k] <= u below a, > u from b on
+    while (a < b) { const uint32_t m = (a + b) >> 1; if (cdf[m] <= u) a = m + 1; else b = m; }
+    const uint32_t lo = a > 0 ? a - 1 : 0, hi = a < Tb - 1 ? a : Tb - 1;
+    const float c0 = cdf[lo];
+    float denom = cdf[hi] - c0;
+    if (denom < 1e-5f) denom = 1.0f;
+    const float t = (u - c0) / denom;
+    const float b0 = bins(lo), b1 = bins(hi);
+    return fminf(b0 + t * (b1 - b0), b1);                                // the min: see the contract (one ulp past the bin's edge at most)
+}
+
+__global__ __launch_bounds__(NV_BLOCK) void k_sample_pdf(const float* __restrict__ bins, const float* __restrict__ weights, uint32_t Tb,
+                                                         const float* __restrict__ u, uint32_t n, nv_pdf_u U, float* __restrict__ out) {
+    extern __shared__ float nv_smem[];
+    long long* scan = reinterpret_cast<long long*>(nv_smem);
+    float* cdf = nv_smem + NV_PDF_SCAN_BYTES / sizeof(float);           // [Tb]
+    const size_t row = blockIdx.x;
+    const float* b = bins + row * Tb;
+    nv_pdf_cdf(weights + row * (Tb - 1), Tb, cdf, scan);
+    for (uint32_t j = threadIdx.x; j < n; j += NV_BLOCK) {
+        const float uj = u ? u[row * n + j] : nv_pdf_u_at(U, j, n);
+        out[row * n + j] = nv_pdf_invert(cdf, Tb, uj, [b](uint32_t k) { return b[k]; });
+    }
+}
+
+// dynamic LDS of k_nav_resample: k_nav_run_fwd's scratch, then the Nc coarse weights.  The cdf [Nc - 1] and the new depths [Nf] reuse the column scratch,
+// which is free once the coarse pass is over (8 + 4096 + 4096 floats of its 16384)
+static size_t nv_resample_lds(uint32_t Nc) { return sizeof(float) * (16 + NV_H * NV_BLOCK + (size_t)Nc); }
+
+__global__ __launch_bounds__(NV_BLOCK) void k_nav_resample(nav_params P, nav_run R, uint32_t Nf, nv_pdf_u U, float* __restrict__ zout,
+                                                           float* __restrict__ wout) {
+    extern __shared__ float nv_smem[];
+    float* lds4 = nv_smem;
+    float* col = nv_smem + 16 + threadIdx.x;
+    float* wts = nv_smem + 16 + NV_H * NV_BLOCK;                         // [Nc]
+    long long* scan = reinterpret_cast<long long*>(nv_smem + 16);
+    float* cdf = nv_smem + 16 + NV_PDF_SCAN_BYTES / sizeof(float);      // [Nc - 1]
+    float* znew = cdf + 4096;                                            // [Nf]
+    const uint32_t n = blockIdx.x, Nc = R.T, T = Nc + Nf;
+    const float ox = R.rays_o[3ull * n], oy = R.rays_o[3ull * n + 1], oz = R.rays_o[3ull * n + 2];
+    const float dx = R.rays_d[3ull * n], dy = R.rays_d[3ull * n + 1], dz = R.rays_d[3ull * n + 2];
+    const float near = R.nears[n], far = R.fars[n], span = far - near;
+
+    // ---- the coarse pass: k_nav_run_fwd's loop down to the weight ----
+    float carry = 1.0f;
+    for (uint32_t c0 = 0; c0 < Nc; c0 += NV_BLOCK) {
+        const uint32_t i = c0 + threadIdx.x;
+        const bool live = i < Nc;
+        const nv_sample s = nv_sample_at(R, live ? i : Nc - 1, near, far, ox, oy, oz, dx, dy, dz);
+        float x0, x1, x2;
+        const bool inside = nv_normalise(P, s.px, s.py, s.pz, x0, x1, x2);
+        float out[16];
+        nv_density_forward<NV_RUN_U>(P, inside, x0, x1, x2, col, out);
+        float ex, alpha, keep;
+        nv_alpha(s.znext_minus_z, P.density_scale, expf(out[0]), ex, alpha, keep);
+        if (!live) { alpha = 0.0f; keep = 1.0f; }
+        float total;
+        const float Tr = carry * nv_block_excl_product(keep, lds4, total);
+        const float w = alpha * Tr;
+        if (live) {
+            wts[i] = w;
+            if (wout) wout[(size_t)n * Nc + i] = w;
+        }
+        carry *= total;
+    }
+    __syncthreads();                                                     // the weights are written; the column scratch is free
+
+    // ---- sample_pdf over w[1 : Nc - 1] and the mid points ----
+    nv_pdf_cdf(wts + 1, Nc - 1, cdf, scan);
+    const auto zc = [near, span, Nc](uint32_t i) { return near + span * nv_lin(i, Nc); };       // nv_sample_at's z, the same bits
+    const auto bin = [&zc](uint32_t k) { const float z0 = zc(k); return z0 + 0.5f * (zc(k + 1) - z0); };      // :183
+    for (uint32_t j = threadIdx.x; j < Nf; j += NV_BLOCK) znew[j] = nv_pdf_invert(cdf, Nc - 1, nv_pdf_u_at(U, j, Nf), bin);
+    __syncthreads();
+
+    // ---- the merge: the stable sort of cat(z, z_new) by ranks; both lists are non-decreasing ----
+    float* zr = zout + (size_t)n * T;
+    for (uint32_t i = threadIdx.x; i < Nc; i += NV_BLOCK) {
+        const float zi = zc(i);
+        uint32_t a = 0, b = Nf;                                          // #{j : z_new_j < z_i}
+        while (a < b) { const uint32_t m = (a + b) >> 1; if (znew[m] < zi) a = m + 1; else b = m; }
+        zr[i + a] = zi;                                                  // i + a <= Nc - 1 + Nf
+    }
+    for (uint32_t j = threadIdx.x; j < Nf; j += NV_BLOCK) {
+        const float v = znew[j];
+        uint32_t a = 0, b = Nc;                                          // #{i : z_i <= z_new_j}
+        while (a < b) { const uint32_t m = (a + b) >> 1; if (zc(m) <= v) a = m + 1; else b = m; }
+        zr[j + a] = v;                                                   // j + a <= Nf - 1 + Nc
+    }
+}
+
+// ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
 
@@ -700,8 +872,9 @@ extern "C" int ngp_nav_field_prepare(const ngp_nav_field_t* f, void* workspace, 
 // the kernels use slightly more than the default 64 KiB of dynamic LDS; the raised limit is a per-device function attribute
 static int nav_allow_big_lds() {
     static std::atomic<unsigned long long> devices{0};
-    const int rc = ngp_allow_dynamic_lds(devices, {(const void*)k_nav_density_fwd, (const void*)k_nav_density_bwd, (const void*)k_nav_run_fwd,
-                                                   (const void*)k_nav_run_bwd, (const void*)k_nav_density_vj}, 160 * 1024);
+    const int rc = ngp_allow_dynamic_lds(devices, {(const void*)k_nav_density_fwd, (const void*)k_nav_density_bwd, (const void*)k_nav_run_fwd<false>,
+                                                   (const void*)k_nav_run_bwd<false>, (const void*)k_nav_density_vj,
+                                                   (const void*)k_nav_run_fwd<true>, (const void*)k_nav_run_bwd<true>, (const void*)k_nav_resample}, 160 * 1024);
     if (rc == NGP_LDS_NO_DEVICE) return ngp_fail(NGP_ELAUNCH, "nav: no current device");
     if (rc != NGP_LDS_OK) return ngp_fail(NGP_ELAUNCH, "nav: cannot raise the dynamic LDS limit");
     return NGP_OK;
@@ -762,45 +935,126 @@ static int nav_run_args(const char* who, const float* rays_o, const float* rays_
     return NGP_OK;
 }
 
-extern "C" int ngp_nav_run_forward(const ngp_nav_field_t* f, const void* prepared, const float* rays_o, const float* rays_d, const float* nears,
-                                   const float* fars, uint32_t N, uint32_t num_steps, const float* aabb_host, const float* bg_color3_host,
-                                   float* image, float* depth, float* weights_sum, void* saved, size_t saved_bytes, void* stream) {
+// the dense run and the run over an explicit depth list share everything on the host but the kernel instantiation: z null = the linspace lattice
+static int nav_run_forward_impl(const char* who, const ngp_nav_field_t* f, const void* prepared, const float* rays_o, const float* rays_d, const float* nears,
+                                const float* fars, uint32_t N, uint32_t T, const float* aabb_host, const float* bg_color3_host, float* image, float* depth,
+                                float* weights_sum, void* saved, size_t saved_bytes, const float* z, uint32_t dist_steps, void* stream) {
     nav_params P;
-    int rc = nav_fill("nav_run_forward", f, prepared, P);
+    int rc = nav_fill(who, f, prepared, P);
     if (rc != NGP_OK) return rc;
     if (N == 0) return NGP_OK;
     nav_run R;
-    rc = nav_run_args("nav_run_forward", rays_o, rays_d, nears, fars, N, num_steps, aabb_host, bg_color3_host, R);
+    rc = nav_run_args(who, rays_o, rays_d, nears, fars, N, T, aabb_host, bg_color3_host, R);
     if (rc != NGP_OK) return rc;
-    NGP_REQUIRE(image && depth && weights_sum, "nav_run_forward: null output");
-    const auto kept = nav_saved_layout(N, num_steps, saved);
-    NGP_REQUIRE(!saved || saved_bytes >= kept.total, "nav_run_forward: `saved` is smaller than ngp_nav_run_saved_bytes(N, num_steps)");
+    NGP_REQUIRE(image && depth && weights_sum, "%s: null output", who);
+    const auto kept = nav_saved_layout(N, T, saved);
+    NGP_REQUIRE(!saved || saved_bytes >= kept.total, "%s: `saved` is smaller than ngp_nav_run_saved_bytes(N, num_steps)", who);
     const size_t lds = sizeof(float) * (16 + NV_H * NV_BLOCK);
     { const int rc_lds = nav_allow_big_lds(); if (rc_lds != NGP_OK) return rc_lds; }
-    hipLaunchKernelGGL(k_nav_run_fwd, dim3(N), dim3(NV_BLOCK), lds, (hipStream_t)stream, P, R, image, depth, weights_sum, kept.p);
-    NGP_CHECK_LAUNCH("nav_run_forward");
+    const nav_at Z = {z, dist_steps};
+    if (z) hipLaunchKernelGGL(k_nav_run_fwd<true>, dim3(N), dim3(NV_BLOCK), lds, (hipStream_t)stream, P, R, image, depth, weights_sum, kept.p, Z);
+    else hipLaunchKernelGGL(k_nav_run_fwd<false>, dim3(N), dim3(NV_BLOCK), lds, (hipStream_t)stream, P, R, image, depth, weights_sum, kept.p, Z);
+    NGP_CHECK_LAUNCH(who);
     return NGP_OK;
+}
+
+static int nav_run_backward_impl(const char* who, const ngp_nav_field_t* f, const void* prepared, const float* rays_o, const float* rays_d,
+                                 const float* nears, const float* fars, uint32_t N, uint32_t T, const float* aabb_host, const float* bg_color3_host,
+                                 const float* grad_image, const float* grad_depth, const float* grad_weights_sum, const void* saved, size_t saved_bytes,
+                                 float* grad_rays_o, float* grad_rays_d, const float* z, uint32_t dist_steps, void* stream) {
+    nav_params P;
+    int rc = nav_fill(who, f, prepared, P);
+    if (rc != NGP_OK) return rc;
+    if (N == 0) return NGP_OK;
+    nav_run R;
+    rc = nav_run_args(who, rays_o, rays_d, nears, fars, N, T, aabb_host, bg_color3_host, R);
+    if (rc != NGP_OK) return rc;
+    NGP_REQUIRE(grad_image && grad_rays_o && grad_rays_d, "%s: null pointer", who);
+    const auto kept = nav_saved_layout(N, T, const_cast<void*>(saved));
+    NGP_REQUIRE(saved && saved_bytes >= kept.total, "%s: needs the `saved` buffer its forward filled", who);
+    const size_t lds = sizeof(float) * (16 + NV_H * NV_BLOCK);
+    { const int rc_lds = nav_allow_big_lds(); if (rc_lds != NGP_OK) return rc_lds; }
+    const nav_at Z = {z, dist_steps};
+    if (z) hipLaunchKernelGGL(k_nav_run_bwd<true>, dim3(N), dim3(NV_BLOCK), lds, (hipStream_t)stream, P, R, grad_image, grad_depth, grad_weights_sum,
+                              (const uint32_t*)kept.p, grad_rays_o, grad_rays_d, Z);
+    else hipLaunchKernelGGL(k_nav_run_bwd<false>, dim3(N), dim3(NV_BLOCK), lds, (hipStream_t)stream, P, R, grad_image, grad_depth, grad_weights_sum,
+                            (const uint32_t*)kept.p, grad_rays_o, grad_rays_d, Z);
+    NGP_CHECK_LAUNCH(who);
+    return NGP_OK;
+}
+
+extern "C" int ngp_nav_run_forward(const ngp_nav_field_t* f, const void* prepared, const float* rays_o, const float* rays_d, const float* nears,
+                                   const float* fars, uint32_t N, uint32_t num_steps, const float* aabb_host, const float* bg_color3_host,
+                                   float* image, float* depth, float* weights_sum, void* saved, size_t saved_bytes, void* stream) {
+    return nav_run_forward_impl("nav_run_forward", f, prepared, rays_o, rays_d, nears, fars, N, num_steps, aabb_host, bg_color3_host, image, depth,
+                                weights_sum, saved, saved_bytes, nullptr, num_steps, stream);
 }
 
 extern "C" int ngp_nav_run_backward(const ngp_nav_field_t* f, const void* prepared, const float* rays_o, const float* rays_d, const float* nears,
                                     const float* fars, uint32_t N, uint32_t num_steps, const float* aabb_host, const float* bg_color3_host,
                                     const float* grad_image, const float* grad_depth, const float* grad_weights_sum, const void* saved,
                                     size_t saved_bytes, float* grad_rays_o, float* grad_rays_d, void* stream) {
+    return nav_run_backward_impl("nav_run_backward", f, prepared, rays_o, rays_d, nears, fars, N, num_steps, aabb_host, bg_color3_host, grad_image,
+                                 grad_depth, grad_weights_sum, saved, saved_bytes, grad_rays_o, grad_rays_d, nullptr, num_steps, stream);
+}
+
+// ---- the resampled run (DESIGN.md §3.5 "Resampled run") ----
+
+extern "C" int ngp_nav_run_at_forward(const ngp_nav_field_t* f, const void* prepared, const float* rays_o, const float* rays_d, const float* nears,
+                                      const float* fars, uint32_t N, uint32_t T, const float* aabb_host, const float* bg_color3_host, float* image,
+                                      float* depth, float* weights_sum, void* saved, size_t saved_bytes, const float* z, uint32_t dist_steps, void* stream) {
+    NGP_REQUIRE(z, "nav_run_at_forward: null depth list z");
+    NGP_REQUIRE(dist_steps >= 1, "nav_run_at_forward: dist_steps must be >= 1");
+    return nav_run_forward_impl("nav_run_at_forward", f, prepared, rays_o, rays_d, nears, fars, N, T, aabb_host, bg_color3_host, image, depth, weights_sum,
+                                saved, saved_bytes, z, dist_steps, stream);
+}
+
+extern "C" int ngp_nav_run_at_backward(const ngp_nav_field_t* f, const void* prepared, const float* rays_o, const float* rays_d, const float* nears,
+                                       const float* fars, uint32_t N, uint32_t T, const float* aabb_host, const float* bg_color3_host,
+                                       const float* grad_image, const float* grad_depth, const float* grad_weights_sum, const void* saved,
+                                       size_t saved_bytes, float* grad_rays_o, float* grad_rays_d, const float* z, uint32_t dist_steps, void* stream) {
+    NGP_REQUIRE(z, "nav_run_at_backward: null depth list z");
+    NGP_REQUIRE(dist_steps >= 1, "nav_run_at_backward: dist_steps must be >= 1");
+    return nav_run_backward_impl("nav_run_at_backward", f, prepared, rays_o, rays_d, nears, fars, N, T, aabb_host, bg_color3_host, grad_image, grad_depth,
+                                 grad_weights_sum, saved, saved_bytes, grad_rays_o, grad_rays_d, z, dist_steps, stream);
+}
+
+// the shape of a resampled run; with N = 0 ngp_nav_run_resample judges field, shape and z and queues nothing (nav_filter.hip asks that way)
+static int nav_resample_shape(const char* who, uint32_t num_steps, uint32_t upsample_steps) {
+    NGP_REQUIRE(num_steps >= 3, "%s: num_steps = %u; the resampled run needs num_steps >= 3", who, num_steps);
+    NGP_REQUIRE(upsample_steps >= 1, "%s: upsample_steps = 0; use the dense entry point", who);
+    NGP_REQUIRE((uint64_t)num_steps + upsample_steps <= 4096, "%s: num_steps + upsample_steps = %u + %u; supported <= 4096", who, num_steps, upsample_steps);
+    return NGP_OK;
+}
+
+extern "C" int ngp_nav_run_resample(const ngp_nav_field_t* f, const void* prepared, const float* rays_o, const float* rays_d, const float* nears,
+                                    const float* fars, uint32_t N, uint32_t num_steps, uint32_t upsample_steps, const float* aabb_host, float* z,
+                                    float* coarse_weights, void* stream) {
     nav_params P;
-    int rc = nav_fill("nav_run_backward", f, prepared, P);
+    int rc = nav_fill("nav_run_resample", f, prepared, P);
     if (rc != NGP_OK) return rc;
+    rc = nav_resample_shape("nav_run_resample", num_steps, upsample_steps);
+    if (rc != NGP_OK) return rc;
+    NGP_REQUIRE(z, "nav_run_resample: null depth list z");
     if (N == 0) return NGP_OK;
     nav_run R;
-    rc = nav_run_args("nav_run_backward", rays_o, rays_d, nears, fars, N, num_steps, aabb_host, bg_color3_host, R);
+    rc = nav_run_args("nav_run_resample", rays_o, rays_d, nears, fars, N, num_steps, aabb_host, nullptr, R);
     if (rc != NGP_OK) return rc;
-    NGP_REQUIRE(grad_image && grad_rays_o && grad_rays_d, "nav_run_backward: null pointer");
-    const auto kept = nav_saved_layout(N, num_steps, const_cast<void*>(saved));
-    NGP_REQUIRE(saved && saved_bytes >= kept.total, "nav_run_backward: needs the `saved` buffer its forward filled");
-    const size_t lds = sizeof(float) * (16 + NV_H * NV_BLOCK);
     { const int rc_lds = nav_allow_big_lds(); if (rc_lds != NGP_OK) return rc_lds; }
-    hipLaunchKernelGGL(k_nav_run_bwd, dim3(N), dim3(NV_BLOCK), lds, (hipStream_t)stream, P, R, grad_image, grad_depth, grad_weights_sum,
-                       (const uint32_t*)kept.p, grad_rays_o, grad_rays_d);
-    NGP_CHECK_LAUNCH("nav_run_backward");
+    const nv_pdf_u U = nv_pdf_u_of(upsample_steps);
+    hipLaunchKernelGGL(k_nav_resample, dim3(N), dim3(NV_BLOCK), nv_resample_lds(num_steps), (hipStream_t)stream, P, R, upsample_steps, U, z, coarse_weights);
+    NGP_CHECK_LAUNCH("nav_run_resample");
+    return NGP_OK;
+}
+
+extern "C" int ngp_sample_pdf(const float* bins, const float* weights, uint32_t N, uint32_t Tb, const float* u, uint32_t n, float* out, void* stream) {
+    NGP_REQUIRE(Tb >= 2 && Tb <= 4096, "sample_pdf: Tb = %u bins; supported 2 <= Tb <= 4096", Tb);
+    NGP_REQUIRE(n >= 1, "sample_pdf: n = 0 samples");
+    if (N == 0) return NGP_OK;
+    NGP_REQUIRE(bins && weights && out, "sample_pdf: null pointer");
+    const nv_pdf_u U = nv_pdf_u_of(n);
+    hipLaunchKernelGGL(k_sample_pdf, dim3(N), dim3(NV_BLOCK), sizeof(float) * Tb + NV_PDF_SCAN_BYTES, (hipStream_t)stream, bins, weights, Tb, u, n, U, out);
+    NGP_CHECK_LAUNCH("sample_pdf");
     return NGP_OK;
 }
 

@@ -20,6 +20,10 @@
 // and differentiates through ngp_nav_run_occ_forward / _backward (nav_field.hip); ngp_filter_iterations_occ and ngp_filter_hessian_occ are the entry points
 // that pass one.  The entry points without a grid keep their code path.
 //
+// Resampled sampling (DESIGN.md §3.5 "Resampled run"): nf_measure takes an optional nf_res (upsample_steps and the caller's depth list) and then queues
+// ngp_nav_run_resample after the rays and renders and differentiates through ngp_nav_run_at_forward / _backward over that list: six launches per iteration.
+// ngp_filter_iterations_res and ngp_filter_hessian_res are the entry points that pass one; the workspace is the dense layout at num_steps + upsample_steps.
+//
 // The derivative conventions are torch autograd's of the formula as written (nav/math_utils.py:159-174): R = I + sin(a) K + ((1 - cos(a)) K) K,
 // K = hat(r / (1e-10 + a)), a = |r|, with the denominator's dependence on a kept and a zero subgradient of the norm at r = 0.  No gradient flows through
 // near / far (nerf/renderer.py:140-141).  No atomics; every sum runs in a fixed order, so two runs are bit-identical.
@@ -401,18 +405,26 @@ extern "C" int ngp_filter_rays(const ngp_filter_cfg_t* c, const float* state, co
     return NGP_OK;
 }
 
+// the resampled route (DESIGN.md §3.5 "Resampled run"): upsample_steps and the caller's depth list [rays, num_steps + Nf]
+struct nf_res { uint32_t Nf; float* z; };
+
 // what the two entry points of the loop do before they queue anything, in this order: the view, the shape, the entry point's own null-pointer refusal
 // (`null_refusal`: its message, or NULL where every pointer is there), the workspace, the field (N = 0 validates and launches nothing), and the
 // start state and inverse covariance the last kernel takes as arguments (A.adam is left zeroed).  K hypotheses (1: the single loop and the Hessian) size
 // the workspace, whose size function `ws_fn` names.  grid: null for the dense run; else the occupancy-masked run's grid, judged with the field
+// res: null, or the resampled route: its shape, z and the field are judged by ngp_nav_run_resample with no rays, and the workspace holds num_steps + Nf samples per ray
 static int nf_begin(const char* who, const char* null_refusal, const ngp_nav_field_t* field, const void* prepared, const ngp_filter_cfg_t* c, uint32_t K,
                     const char* ws_fn, void* workspace, size_t workspace_bytes, void* stream, nf_view& V, nf_ws& w, nf_step_args& A,
-                    const ngp_occ_grid_t* grid = nullptr) {
+                    const ngp_occ_grid_t* grid = nullptr, const nf_res* res = nullptr) {
     const int rc_v = nf_view_of(who, c, V);
     if (rc_v != NGP_OK) return rc_v;
-    const uint32_t T = c->num_steps;
-    NGP_REQUIRE(T >= 1 && T <= NF_MAX_T, "%s: num_steps = %u; supported 1 <= num_steps <= 4096", who, T);
+    NGP_REQUIRE(c->num_steps >= 1 && c->num_steps <= NF_MAX_T, "%s: num_steps = %u; supported 1 <= num_steps <= 4096", who, c->num_steps);
     NGP_REQUIRE(!null_refusal, "%s", null_refusal);
+    if (res) {                                                               // the resampled run's own refusals (shape, z, the field): N = 0 queues nothing
+        const int rc_r = ngp_nav_run_resample(field, prepared, nullptr, nullptr, nullptr, nullptr, 0, c->num_steps, res->Nf, c->aabb, res->z, nullptr, stream);
+        if (rc_r != NGP_OK) return rc_r;
+    }
+    const uint32_t T = c->num_steps + (res ? res->Nf : 0u);                  // samples per ray of the differentiated run
     w = nf_multi_layout(K, c->B, T, workspace, grid != nullptr);
     if (!workspace || workspace_bytes < w.total)
         return ngp_fail(NGP_EWORKSPACE, "%s: workspace of %zu bytes, needs %s = %zu", who, workspace_bytes, ws_fn, w.total);
@@ -435,15 +447,23 @@ static int nf_launched(const char* who, const char* what) {
 // the measurement pass at `state` for one batch: rays -> run forward -> loss -> run backward, queued; leaves grad_rays_o, grad_rays_d and the loss partials in w.
 // K = 0: one state, the single kernels; K >= 1: `state` is [K,12] and the multi kernels fill K slices, with the run kernels launched once over K B rays.
 // grid: null = the dense run; else the occupancy-masked pair renders and differentiates (w laid out with occ)
+// res: null, or the resampled route: ngp_nav_run_resample fills res->z after the rays, and the run over that list renders and differentiates
 static int nf_measure(const char* who, const ngp_nav_field_t* field, const void* prepared, const ngp_filter_cfg_t* c, const nf_view& V, const nf_ws& w,
-                      uint32_t K, const float* state, const float* target, const int32_t* batch, void* stream, const ngp_occ_grid_t* grid = nullptr) {
-    const uint32_t B = c->B, T = c->num_steps, blocks = ngp_div_up(B, NF_THREADS), N = (K ? K : 1u) * B;
+                      uint32_t K, const float* state, const float* target, const int32_t* batch, void* stream, const ngp_occ_grid_t* grid = nullptr,
+                      const nf_res* res = nullptr) {
+    const uint32_t B = c->B, T = c->num_steps + (res ? res->Nf : 0u), blocks = ngp_div_up(B, NF_THREADS), N = (K ? K : 1u) * B;
     hipStream_t s = (hipStream_t)stream;
     if (K) hipLaunchKernelGGL(k_filter_rays_multi, dim3(blocks, K), dim3(NF_THREADS), 0, s, V, state, batch, B, w.rays_o, w.rays_d, w.nears, w.fars);
     else hipLaunchKernelGGL(k_filter_rays, dim3(blocks), dim3(NF_THREADS), 0, s, V, state, batch, B, w.rays_o, w.rays_d, w.nears, w.fars);
     int rc = nf_launched(who, "rays");
     if (rc != NGP_OK) return rc;
-    rc = grid ? ngp_nav_run_occ_forward(field, prepared, grid, w.rays_o, w.rays_d, w.nears, w.fars, N, T, c->aabb, c->bg, w.image, w.depth, w.weights_sum,
+    if (res) {                                                               // the sixth launch: this iteration's depth lists
+        rc = ngp_nav_run_resample(field, prepared, w.rays_o, w.rays_d, w.nears, w.fars, N, c->num_steps, res->Nf, c->aabb, res->z, nullptr, stream);
+        if (rc != NGP_OK) return rc;
+    }
+    rc = res  ? ngp_nav_run_at_forward(field, prepared, w.rays_o, w.rays_d, w.nears, w.fars, N, T, c->aabb, c->bg, w.image, w.depth, w.weights_sum, w.saved,
+                                       w.saved_bytes, res->z, c->num_steps, stream)
+       : grid ? ngp_nav_run_occ_forward(field, prepared, grid, w.rays_o, w.rays_d, w.nears, w.fars, N, T, c->aabb, c->bg, w.image, w.depth, w.weights_sum,
                                         nullptr, w.saved, w.saved_bytes, stream)
               : ngp_nav_run_forward(field, prepared, w.rays_o, w.rays_d, w.nears, w.fars, N, T, c->aabb, c->bg, w.image, w.depth, w.weights_sum, w.saved,
                                     w.saved_bytes, stream);
@@ -452,6 +472,9 @@ static int nf_measure(const char* who, const ngp_nav_field_t* field, const void*
     else hipLaunchKernelGGL(k_filter_loss, dim3(blocks), dim3(NF_THREADS), 0, s, (const float*)w.image, target, batch, B, c->H, c->W, w.grad_image, w.partials);
     rc = nf_launched(who, "loss");
     if (rc != NGP_OK) return rc;
+    if (res)
+        return ngp_nav_run_at_backward(field, prepared, w.rays_o, w.rays_d, w.nears, w.fars, N, T, c->aabb, c->bg, w.grad_image, nullptr, nullptr, w.saved,
+                                       w.saved_bytes, w.grad_rays_o, w.grad_rays_d, res->z, c->num_steps, stream);
     if (grid)
         return ngp_nav_run_occ_backward(field, prepared, grid, w.rays_o, w.rays_d, w.nears, w.fars, N, T, c->aabb, c->bg, w.grad_image, nullptr, nullptr,
                                         w.saved, w.saved_bytes, w.grad_rays_o, w.grad_rays_d, stream);
@@ -487,7 +510,7 @@ extern "C" int ngp_filter_iterations(const ngp_nav_field_t* field, const void* p
 static int nf_iterations_multi(const char* who, const char* null_refusal, const char* ws_fn, const ngp_nav_field_t* field, const void* prepared,
                                const ngp_filter_cfg_t* c, const ngp_occ_grid_t* grid, uint32_t K, float* states, float* adam_states, const float* target,
                                const int32_t* batches, uint32_t first_iter, uint32_t n_iter, int update, float* losses, float* states_out, float* grads_out,
-                               void* workspace, size_t workspace_bytes, void* stream) {
+                               void* workspace, size_t workspace_bytes, void* stream, const nf_res* res = nullptr) {
     NGP_REQUIRE(K >= 1 && K <= NGP_FILTER_MULTI_MAX_K, "%s: K = %u hypotheses; supported 1 <= K <= %u", who, K, NGP_FILTER_MULTI_MAX_K);
     NGP_REQUIRE(!c || c->B > NF_MAX_B || (uint64_t)K * c->B <= NF_MAX_B, "%s: K * B = %u * %u rays per iteration; supported K * B <= 2^20", who,
                 K, c ? c->B : 0u);
@@ -495,13 +518,13 @@ static int nf_iterations_multi(const char* who, const char* null_refusal, const 
     nf_ws w;
     nf_step_args A;
     int rc = nf_begin(who, states && adam_states && target && batches ? nullptr : null_refusal, field, prepared, c, K, ws_fn, workspace, workspace_bytes,
-                      stream, V, w, A, grid);
+                      stream, V, w, A, grid, res);
     if (rc != NGP_OK) return rc;
     A.adam = ngp_adam_fill(c->lr, c->beta1, c->beta2, c->eps);
     const uint32_t B = c->B, blocks = ngp_div_up(B, NF_THREADS);
     for (uint32_t k = 0; k < n_iter; k++) {
         const int32_t* batch = batches + 2 * (size_t)B * ((size_t)first_iter + k);
-        rc = nf_measure(who, field, prepared, c, V, w, K, states, target, batch, stream, grid);
+        rc = nf_measure(who, field, prepared, c, V, w, K, states, target, batch, stream, grid, res);
         if (rc != NGP_OK) return rc;
         const size_t row = (size_t)k * K;
         hipLaunchKernelGGL(k_filter_step_multi, dim3(K), dim3(NF_THREADS), 0, (hipStream_t)stream, V, A, update, states, adam_states, batch, B,
@@ -661,14 +684,14 @@ extern "C" int ngp_filter_propagate(const ngp_filter_dyn_t* dyn, const float* st
 
 static int nf_hessian(const char* who, const char* null_refusal, const char* ws_fn, const ngp_nav_field_t* field, const void* prepared,
                       const ngp_filter_cfg_t* c, const ngp_occ_grid_t* grid, const float* state, const float* target, const int32_t* batch, float* hessian,
-                      float* grad, float* loss, float* dLdP, void* workspace, size_t workspace_bytes, void* stream) {
+                      float* grad, float* loss, float* dLdP, void* workspace, size_t workspace_bytes, void* stream, const nf_res* res = nullptr) {
     nf_view V;
     nf_ws w;
     nf_step_args A;
     int rc = nf_begin(who, state && target && batch && hessian ? nullptr : null_refusal, field, prepared, c, 1, ws_fn, workspace, workspace_bytes, stream, V, w,
-                      A, grid);
+                      A, grid, res);
     if (rc != NGP_OK) return rc;
-    rc = nf_measure(who, field, prepared, c, V, w, 0, state, target, batch, stream, grid);
+    rc = nf_measure(who, field, prepared, c, V, w, 0, state, target, batch, stream, grid, res);
     if (rc != NGP_OK) return rc;
     hipLaunchKernelGGL(k_filter_hessian, dim3(1), dim3(NF_THREADS), 0, (hipStream_t)stream, V, A, state, batch, c->B, (const float*)w.grad_rays_o,
                        (const float*)w.grad_rays_d, (const float*)w.partials, ngp_div_up(c->B, NF_THREADS), hessian, grad, loss, dLdP);
@@ -688,4 +711,24 @@ extern "C" int ngp_filter_hessian_occ(const ngp_nav_field_t* field, const void* 
     NGP_REQUIRE(grid, "filter_hessian_occ: null occupancy grid");
     return nf_hessian("filter_hessian_occ", "filter_hessian_occ: null state / target / batch / hessian", "ngp_filter_occ_workspace(1, B, num_steps)", field,
                       prepared, c, grid, state, target, batch, hessian, grad, loss, dLdP, workspace, workspace_bytes, stream);
+}
+
+// ---- the resampled route: the same loop and Hessian with ngp_nav_run_resample + the run over its depth list in the measurement pass ----
+
+extern "C" int ngp_filter_iterations_res(const ngp_nav_field_t* field, const void* prepared, const ngp_filter_cfg_t* c, uint32_t K, float* states,
+                                         float* adam_states, const float* target, const int32_t* batches, uint32_t first_iter, uint32_t n_iter, int update,
+                                         float* losses, float* states_out, float* grads_out, void* workspace, size_t workspace_bytes, uint32_t upsample_steps,
+                                         float* z, void* stream) {
+    const nf_res res = {upsample_steps, z};
+    return nf_iterations_multi("filter_iterations_res", "filter_iterations_res: null states / adam_states / target / batches",
+                               "ngp_filter_multi_workspace(K, B, num_steps + upsample_steps)", field, prepared, c, nullptr, K, states, adam_states, target,
+                               batches, first_iter, n_iter, update, losses, states_out, grads_out, workspace, workspace_bytes, stream, &res);
+}
+
+extern "C" int ngp_filter_hessian_res(const ngp_nav_field_t* field, const void* prepared, const ngp_filter_cfg_t* c, const float* state, const float* target,
+                                      const int32_t* batch, float* hessian, float* grad, float* loss, float* dLdP, void* workspace, size_t workspace_bytes,
+                                      uint32_t upsample_steps, float* z, void* stream) {
+    const nf_res res = {upsample_steps, z};
+    return nf_hessian("filter_hessian_res", "filter_hessian_res: null state / target / batch / hessian", "ngp_filter_workspace(B, num_steps + upsample_steps)",
+                      field, prepared, c, nullptr, state, target, batch, hessian, grad, loss, dLdP, workspace, workspace_bytes, stream, &res);
 }

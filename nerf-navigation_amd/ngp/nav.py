@@ -396,11 +396,67 @@ class _nav_run_occ(torch.autograd.Function):
         return go, gd, None, None, None, None
 
 
+class _nav_run_resampled(torch.autograd.Function):
+    """NeRFRenderer.run(num_steps, upsample_steps > 0, perturb = False) with sample_pdf's deterministic branch (DESIGN 3.5 "Resampled run"): one launch
+    for the coarse pass, the inverse CDF and the merge (ngp_nav_run_resample), one for the run over the merged depth list, one backward to the rays.
+    The depth list is a constant (nerf/renderer.py:173, :184), so the gradients are those of the run at fixed depths; second derivatives as for
+    _nav_run: graph-less gradient tensors.  The saved record is kept only when a gradient is needed."""
+
+    @staticmethod
+    def forward(ctx, rays_o, rays_d, owner, num_steps, upsample_steps, bg):
+        import ctypes
+        import raymarching
+        import ngp_hip as _hip
+        rays_o, rays_d = rays_o.contiguous().float(), rays_d.contiguous().float()
+        N, Nc, Nf = rays_o.shape[0], int(num_steps), int(upsample_steps)
+        T = Nc + Nf
+        ren = owner.renderer
+        nears, fars = raymarching.near_far_from_aabb(rays_o, rays_d, ren._aabb(), ren.min_near)
+        aabb = (ctypes.c_float * 6)(*ren._aabb_host())
+        bgc = (ctypes.c_float * 3)(*bg)
+        kw = dict(dtype=torch.float32, device=rays_o.device)
+        image, depth, ws = torch.empty(N, 3, **kw), torch.empty(N, **kw), torch.empty(N, **kw)
+        z = torch.empty(N, max(T, 1), **kw)
+        st, prep = owner.struct()
+        L = _hip.lib()
+        need = any(ctx.needs_input_grad[:2])
+        with torch.cuda.device(rays_o.device):
+            with _hip.timed("nav_run_resample"):
+                _hip.check(L.ngp_nav_run_resample(ctypes.byref(st), _hip.ptr(prep), _hip.ptr(rays_o), _hip.ptr(rays_d), _hip.ptr(nears), _hip.ptr(fars),
+                                                  N, Nc, Nf, aabb, _hip.ptr(z), None, _hip.stream()), "nav_run_resample")
+            saved = _hip.workspace(L.ngp_nav_run_saved_bytes(N, T), rays_o.device) if need else None
+            with _hip.timed("nav_run_at_forward"):
+                _hip.check(L.ngp_nav_run_at_forward(ctypes.byref(st), _hip.ptr(prep), _hip.ptr(rays_o), _hip.ptr(rays_d), _hip.ptr(nears), _hip.ptr(fars),
+                                                    N, T, aabb, bgc, _hip.ptr(image), _hip.ptr(depth), _hip.ptr(ws), _hip.ptr(saved),
+                                                    saved.numel() if need else 0, _hip.ptr(z), Nc, _hip.stream()), "nav_run_at_forward")
+        ctx.save_for_backward(rays_o, rays_d, nears, fars, saved if need else torch.empty(0, device=rays_o.device), z)
+        ctx.owner, ctx.steps, ctx.bg, ctx.aabb = owner, (Nc, T), bgc, aabb
+        return image, depth, ws
+
+    @staticmethod
+    def backward(ctx, g_image, g_depth, g_ws):
+        import ctypes
+        import ngp_hip as _hip
+        rays_o, rays_d, nears, fars, saved, z = ctx.saved_tensors
+        g_image, g_depth, g_ws = g_image.detach(), g_depth.detach(), g_ws.detach()
+        N = rays_o.shape[0]
+        Nc, T = ctx.steps
+        go, gd = torch.empty_like(rays_o), torch.empty_like(rays_d)
+        st, prep = ctx.owner.struct()
+        with torch.cuda.device(rays_o.device), _hip.timed("nav_run_at_backward"):
+            _hip.check(_hip.lib().ngp_nav_run_at_backward(ctypes.byref(st), _hip.ptr(prep), _hip.ptr(rays_o), _hip.ptr(rays_d), _hip.ptr(nears),
+                                                          _hip.ptr(fars), N, T, ctx.aabb, ctx.bg, _hip.ptr(g_image.contiguous().float()),
+                                                          _hip.ptr(g_depth.contiguous().float()), _hip.ptr(g_ws.contiguous().float()), _hip.ptr(saved),
+                                                          saved.numel(), _hip.ptr(go), _hip.ptr(gd), _hip.ptr(z), Nc, _hip.stream()), "nav_run_at_backward")
+        return go, gd, None, None, None, None
+
+
 class NativeNavQueries(NavQueries):
     """NavQueries on the fused float32 kernels (csrc/nav_field.hip): `density_fn` = one launch (+ one for its gradient), `render_fn` = one
     launch per max_ray_batch rays (+ one for the gradient to the rays) instead of ~130 launches per filter iteration.  Same interface and
     the same results to float32 rounding (tests/test_gpu_nav_native.py compares both with the CPU oracle).  Needs the default field
-    (ngp.field.NGPField) in float32 and upsample_steps == 0 (what simulate.py uses); anything else: use NavQueries."""
+    (ngp.field.NGPField) in float32 and upsample_steps == 0 (what simulate.py uses); anything else: use NavQueries.  The importance-resampled run
+    (upsample_steps > 0, deterministic sample_pdf) is the method render_fn_resampled, not a constructor argument."""
 
     def __init__(self, renderer, intrinsics, H, W, num_steps=512, upsample_steps=0, max_ray_batch=4096, freeze=True):
         super().__init__(renderer, intrinsics, H, W, num_steps=num_steps, upsample_steps=upsample_steps, max_ray_batch=max_ray_batch, freeze=freeze)
@@ -438,6 +494,24 @@ class NativeNavQueries(NavQueries):
             for head in range(0, N, self.max_ray_batch):
                 tail = min(head + self.max_ray_batch, N)
                 img, dep, _ = _nav_run.apply(rays_o[b, head:tail], rays_d[b, head:tail], self.native, self.num_steps, (1.0, 1.0, 1.0))
+                images.append(img)
+                depths.append(dep)
+        return {"image": torch.cat(images).view(B, N, 3), "depth": torch.cat(depths).view(B, N)}
+
+    def render_fn_resampled(self, rays_o, rays_d, upsample_steps, num_steps=None):
+        """render_fn with NeRFRenderer.run's importance resampling (DESIGN 3.5 "Resampled run"): num_steps (default: the queries') coarse samples per ray,
+        then `upsample_steps` depths drawn from the coarse weights' pdf (sample_pdf, deterministic branch), all composited in depth order.  Same dict and
+        the same chunking as render_fn; gradients to the rays at fixed depths, as the reference's."""
+        Nc = self.num_steps if num_steps is None else int(num_steps)
+        Nf = int(upsample_steps)
+        if Nc < 3 or Nf < 1 or Nc + Nf > 4096:
+            raise ValueError(f"render_fn_resampled needs num_steps >= 3, upsample_steps >= 1 and at most 4096 samples per ray, got {Nc} + {Nf}")
+        B, N = rays_o.shape[:2]
+        images, depths = [], []
+        for b in range(B):
+            for head in range(0, N, self.max_ray_batch):
+                tail = min(head + self.max_ray_batch, N)
+                img, dep, _ = _nav_run_resampled.apply(rays_o[b, head:tail], rays_d[b, head:tail], self.native, Nc, Nf, (1.0, 1.0, 1.0))
                 images.append(img)
                 depths.append(dep)
         return {"image": torch.cat(images).view(B, N, 3), "depth": torch.cat(depths).view(B, N)}
@@ -1021,9 +1095,9 @@ class _KeywordSampling(type):
     """NativePoseFilter(..., sampling=...): a keyword-only option taken here, so that the constructor's positional parameters (filter_cfg, queries,
     start_state, agent_cfg -- in that order, agent_cfg last) stay what their callers and tests/test_filter_step_host.py rely on."""
 
-    def __call__(cls, *args, sampling="dense", **kwargs):
+    def __call__(cls, *args, sampling="dense", upsample_steps=None, **kwargs):
         self = super().__call__(*args, **kwargs)
-        self.set_sampling(sampling)
+        self.set_sampling(sampling, upsample_steps=upsample_steps)
         return self
 
 
@@ -1061,6 +1135,10 @@ class NativePoseFilter(metaclass=_KeywordSampling):
     Hessian, and so estimate_state -- renders through the renderer's occupancy grid (ngp_filter_iterations_occ / ngp_filter_hessian_occ): the sigma of a
     lattice sample in an empty grid cell is zero and the field is evaluated at the occupied samples only.  A different objective from the dense one
     (the sensor's model of empty space); needs a renderer built with cuda_ray=True.  The default "dense" is the route above, unchanged.
+
+    sampling="resampled", upsample_steps=n (DESIGN 3.5 "Resampled run"): every measurement pass renders NeRFRenderer.run's importance-resampled variant:
+    the queries' num_steps coarse samples, n more drawn from the coarse weights' pdf, composited together (ngp_filter_iterations_res /
+    ngp_filter_hessian_res, six launches per iteration).  Another objective again; needs no occupancy grid.
     """
 
     def __init__(self, filter_cfg, queries, start_state=None, agent_cfg=None):
@@ -1085,13 +1163,23 @@ class NativePoseFilter(metaclass=_KeywordSampling):
         self._feat_ws = self._seed0 = None
         self.multi = None                                    # the hypotheses of the last multi-start run (estimate_relative_pose_multi)
         self._ws_multi = self._ws_occ = None
+        self.upsample_steps = 0                              # of sampling="resampled"
+        self._ws_res = self._z_res = None
 
-    def set_sampling(self, sampling):
-        """"dense": every sample of the lattice (the default route); "occupied": the samples in occupied grid cells only (the class docstring)"""
-        if sampling not in ("dense", "occupied"):
-            raise ValueError(f"sampling must be 'dense' or 'occupied', got {sampling!r}")
+    def set_sampling(self, sampling, upsample_steps=None):
+        """"dense": every sample of the lattice (the default route); "occupied": the samples in occupied grid cells only; "resampled": the lattice plus
+        `upsample_steps` importance samples per ray (the class docstring)"""
+        if sampling not in ("dense", "occupied", "resampled"):
+            raise ValueError(f"sampling must be 'dense', 'occupied' or 'resampled', got {sampling!r}")
         if sampling == "occupied":
             occupancy_grid(self.queries.renderer)            # ValueError unless the renderer holds a grid (cuda_ray=True)
+        if sampling == "resampled":
+            Nc, Nf = int(self.queries.num_steps), int(upsample_steps or 0)
+            if Nc < 3 or Nf < 1 or Nc + Nf > 4096:
+                raise ValueError(f"sampling='resampled' needs num_steps >= 3, upsample_steps >= 1 and at most 4096 samples per ray, got {Nc} + {Nf}")
+            self.upsample_steps = Nf
+        elif upsample_steps:
+            raise ValueError("upsample_steps belongs to sampling='resampled'")
         self.sampling = sampling
 
     # -- plumbing ------------------------------------------------------------------------------------------------------
@@ -1155,6 +1243,19 @@ class NativePoseFilter(metaclass=_KeywordSampling):
         grid, bits = occupancy_grid(self.queries.renderer)
         return self._ws_occ, grid, bits
 
+    def _workspace_res(self, K, B):
+        """the workspace and the depth list [K B, T] of the resampled route (kept, grown on demand)"""
+        import ngp_hip as _hip
+        T = int(self.queries.num_steps) + self.upsample_steps
+        nbytes = _hip.lib().ngp_filter_multi_workspace(int(K), int(B), T)
+        if nbytes == 0:
+            raise ValueError(f"{K} hypotheses of {B} rays: supported 1 <= K <= {_hip.FILTER_MULTI_MAX_K} and K * B <= 2^20")
+        if self._ws_res is None or self._ws_res.numel() < nbytes:
+            self._ws_res = _hip.workspace(nbytes, self.device)
+        if self._z_res is None or self._z_res.numel() < int(K) * int(B) * T:
+            self._z_res = torch.empty(int(K) * int(B) * T, dtype=torch.float32, device=self.device)
+        return self._ws_res, self._z_res
+
     def new_adam_state(self):
         """zeroed Adam moments and step: the reference builds a new optimiser in every estimate_relative_pose"""
         import ngp_hip as _hip
@@ -1186,6 +1287,13 @@ class NativePoseFilter(metaclass=_KeywordSampling):
                                                             _hip.ptr(adam_state), _hip.ptr(target), _hip.ptr(batches), int(first_iter), int(n_iter),
                                                             1 if update else 0, _hip.ptr(losses), _hip.ptr(states), _hip.ptr(grads), _hip.ptr(ws),
                                                             ws.numel(), _hip.stream()), "filter_iterations_occ")
+            return
+        if self.sampling == "resampled":                     # K = 1 of the resampled loop, likewise
+            ws, z = self._workspace_res(1, B)
+            _hip.check(_hip.lib().ngp_filter_iterations_res(ctypes.byref(st), _hip.ptr(prep), ctypes.byref(c), 1, _hip.ptr(state), _hip.ptr(adam_state),
+                                                            _hip.ptr(target), _hip.ptr(batches), int(first_iter), int(n_iter), 1 if update else 0,
+                                                            _hip.ptr(losses), _hip.ptr(states), _hip.ptr(grads), _hip.ptr(ws), ws.numel(),
+                                                            self.upsample_steps, _hip.ptr(z), _hip.stream()), "filter_iterations_res")
             return
         ws = self._workspace(B)
         _hip.check(_hip.lib().ngp_filter_iterations(ctypes.byref(st), _hip.ptr(prep), ctypes.byref(c), _hip.ptr(state), _hip.ptr(adam_state),
@@ -1351,6 +1459,13 @@ class NativePoseFilter(metaclass=_KeywordSampling):
                                                             1 if update else 0, _hip.ptr(losses), _hip.ptr(states_out), _hip.ptr(grads), _hip.ptr(ws),
                                                             ws.numel(), _hip.stream()), "filter_iterations_occ")
             return
+        if self.sampling == "resampled":
+            ws, z = self._workspace_res(K, B)
+            _hip.check(_hip.lib().ngp_filter_iterations_res(ctypes.byref(st), _hip.ptr(prep), ctypes.byref(c), K, _hip.ptr(states), _hip.ptr(adam_states),
+                                                            _hip.ptr(target), _hip.ptr(batches), int(first_iter), int(n_iter), 1 if update else 0,
+                                                            _hip.ptr(losses), _hip.ptr(states_out), _hip.ptr(grads), _hip.ptr(ws), ws.numel(),
+                                                            self.upsample_steps, _hip.ptr(z), _hip.stream()), "filter_iterations_res")
+            return
         ws = self._workspace_multi(K, B)
         _hip.check(_hip.lib().ngp_filter_iterations_multi(ctypes.byref(st), _hip.ptr(prep), ctypes.byref(c), K, _hip.ptr(states), _hip.ptr(adam_states),
                                                           _hip.ptr(target), _hip.ptr(batches), int(first_iter), int(n_iter), 1 if update else 0,
@@ -1479,6 +1594,14 @@ class NativePoseFilter(metaclass=_KeywordSampling):
                                                          _hip.ptr(self._vec(state).contiguous()), _hip.ptr(target), _hip.ptr(batch), _hip.ptr(out["hessian"]),
                                                          _hip.ptr(out["grad"]), _hip.ptr(out["loss"]), _hip.ptr(out["dLdP"]), _hip.ptr(ws), ws.numel(),
                                                          _hip.stream()), "filter_hessian_occ")
+            out["loss"] = out["loss"][0]
+            return out
+        if self.sampling == "resampled":
+            ws, z = self._workspace_res(1, B)
+            _hip.check(_hip.lib().ngp_filter_hessian_res(ctypes.byref(st), _hip.ptr(prep), ctypes.byref(c), _hip.ptr(self._vec(state).contiguous()),
+                                                         _hip.ptr(target), _hip.ptr(batch), _hip.ptr(out["hessian"]), _hip.ptr(out["grad"]),
+                                                         _hip.ptr(out["loss"]), _hip.ptr(out["dLdP"]), _hip.ptr(ws), ws.numel(), self.upsample_steps,
+                                                         _hip.ptr(z), _hip.stream()), "filter_hessian_res")
             out["loss"] = out["loss"][0]
             return out
         ws = self._workspace(B)
@@ -1758,7 +1881,7 @@ SIMULATE_FOLDERS = ("init_poses", "init_costs", "replan_poses", "replan_costs", 
 
 
 def simulate(planner_cfg, agent_cfg, filter_cfg, extra_cfg, queries, sensor=None, basefolder=None, generator=None, interest_regions=None, seed=None,
-             filter_offsets=None, planner_starts=None, filter_sampling="dense"):
+             filter_offsets=None, planner_starts=None, filter_sampling="dense", filter_upsample_steps=None):
     """simulate.simulate (simulate.py:18-102) over the native planner, agent and filter: A* and learn_init, then per MPC step the planner's action, the agent's
     noisy step and observation, the filter's time step and, before `steps - 5`, update_state and learn_update.
 
@@ -1768,7 +1891,8 @@ def simulate(planner_cfg, agent_cfg, filter_cfg, extra_cfg, queries, sensor=None
     (features="native", the draw keyed by `seed`) unless interest_regions ([M,2] (row, col)) are given, which are then used every step with
     numpy's default_rng(seed).  seed also seeds a_star_init's path noise; None leaves all three to the global / operating-system sources, as the reference.
     filter_offsets [K,12]: every time step of the filter is the multi-start one (estimate_state's `offsets`); None: the loop as it is.
-    filter_sampling: NativePoseFilter's `sampling` ("dense", or "occupied": the filter renders through the renderer's occupancy grid).
+    filter_sampling: NativePoseFilter's `sampling` ("dense", or "occupied": the filter renders through the renderer's occupancy grid, or "resampled" with
+    filter_upsample_steps: the filter renders the importance-resampled run; the agent's sensor stays as it is).
     planner_starts dict(K=..., amplitude=...): learn_init and every learn_update take the planner's multi-start route from draw_offsets(K, amplitude) at
     the current R, drawn from a generator of their own (seeded by `seed`; the global one when seed is None); None: the loop as it is.
     basefolder: a directory (created when missing) that receives the reference's five sub-folders, init_* and replan_* from the planner, estimator_data/
@@ -1796,7 +1920,7 @@ def simulate(planner_cfg, agent_cfg, filter_cfg, extra_cfg, queries, sensor=None
     start12 = torch.cat([s18[:6], _rot_matrix_to_vec(s18[6:15].reshape(3, 3)), s18[15:]], dim=-1).to(traj.device)
     agent_cfg = dict(agent_cfg, x0=start12)
     agent = NativeAgent(agent_cfg, queries, sensor)
-    filt = NativePoseFilter(filter_cfg, queries, start12, agent_cfg, sampling=filter_sampling)
+    filt = NativePoseFilter(filter_cfg, queries, start12, agent_cfg, sampling=filter_sampling, upsample_steps=filter_upsample_steps)
     steps = int(traj.get_actions().shape[0])
     noise_mean, noise_std = extra_cfg["mpc_noise_mean"], extra_cfg["mpc_noise_std"]
     rng = None if interest_regions is None else np.random.default_rng(seed)

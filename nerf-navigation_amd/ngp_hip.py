@@ -125,6 +125,10 @@ _SIGNATURES = {
     "ngp_nav_run_occ_saved_bytes": (c_sz, [c_u32, c_u32]),
     "ngp_nav_run_occ_forward": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_u32, c_u32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "ngp_nav_run_occ_backward": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_u32, c_u32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp, c_vp, c_vp]),
+    "ngp_sample_pdf": (c_int, [c_vp, c_vp, c_u32, c_u32, c_vp, c_u32, c_vp, c_vp]),
+    "ngp_nav_run_resample": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_u32, c_u32, c_u32, c_vp, c_vp, c_vp, c_vp]),
+    "ngp_nav_run_at_forward": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_u32, c_u32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp, c_u32, c_vp]),
+    "ngp_nav_run_at_backward": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_u32, c_u32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp, c_vp, c_vp, c_u32, c_vp]),
     "ngp_nav_render_frame_workspace": (c_sz, [c_u32]),
     "ngp_nav_render_frame": (c_int, [c_vp, c_vp, c_vp, c_vp, c_u32, c_u32, c_vp, c_f32, c_vp, c_u32, c_u32, c_f32, c_u32, c_vp,
                                      c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
@@ -162,6 +166,8 @@ _SIGNATURES = {
     "ngp_filter_occ_workspace": (c_sz, [c_u32, c_u32, c_u32]),
     "ngp_filter_iterations_occ": (c_int, [c_vp, c_vp, c_vp, c_vp, c_u32, c_vp, c_vp, c_vp, c_vp, c_u32, c_u32, c_int, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "ngp_filter_hessian_occ": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "ngp_filter_iterations_res": (c_int, [c_vp, c_vp, c_vp, c_u32, c_vp, c_vp, c_vp, c_vp, c_u32, c_u32, c_int, c_vp, c_vp, c_vp, c_vp, c_sz, c_u32, c_vp, c_vp]),
+    "ngp_filter_hessian_res": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_u32, c_vp, c_vp]),
     "ngp_features_default_cfg": (None, [c_vp]),
     "ngp_features_workspace": (c_sz, [c_u32, c_u32]),
     "ngp_features_layout": (c_int, [c_u32, c_u32, c_vp]),

@@ -125,8 +125,12 @@ def group_filter(args, dev):
     target = agent.target
     start = x0 + torch.tensor(START_OFFSET, device=dev)
     sig0, Q = 0.1 * torch.eye(12, device=dev), 0.01 * torch.eye(12, device=dev)
-    filt = nav.NativePoseFilter({"batch_size": RAYS, "lrate": 1e-3, "N_iter": args.iters, "sig0": sig0, "Q": Q}, q, start.clone(), cfg,
-                                sampling=args.filter_sampling)
+    qf, steps, kw = q, f"{STEPS} steps", {}
+    if args.filter_sampling == "resampled":                  # the filter's own queries: num_steps coarse samples, then upsample_steps more; the sensor keeps q
+        qf = nav.NativeNavQueries(q.renderer, q.intrinsics, q.H, q.W, num_steps=args.filter_num_steps)
+        steps, kw = f"{args.filter_num_steps} + {args.filter_upsample_steps} steps", {"upsample_steps": args.filter_upsample_steps}
+    filt = nav.NativePoseFilter({"batch_size": RAYS, "lrate": 1e-3, "N_iter": args.iters, "sig0": sig0, "Q": Q}, qf, start.clone(), cfg,
+                                sampling=args.filter_sampling, **kw)
 
     # the front (keypoints, dilation, pixel list) is timed on the observation as it is.  The loop needs batch_size distinct pixels: where this synthetic
     # scene gives the detector fewer, the batches are drawn (natively, on the device) from every pixel of the image instead, and the output says so
@@ -147,7 +151,7 @@ def group_filter(args, dev):
     for _ in range(args.rounds):
         times["filter_step"].append(wall(step)[0])
         times["interest_regions"].append(wall(lambda: filt.interest_regions(target))[0])
-    return {"group": "filter", "case": f"{RAYS} rays x {STEPS} steps, {args.iters} iterations, {args.side} x {args.side} target, {args.rounds} rounds, "
+    return {"group": "filter", "case": f"{RAYS} rays x {steps}, {args.iters} iterations, {args.side} x {args.side} target, {args.rounds} rounds, "
                                        f"{args.filter_sampling} sampling",
             "ms": {k: quartiles(v) for k, v in times.items()}, "interest_pixels": found,
             "batches_drawn_from": "the interest regions (features='native')" if native_front else "every pixel (fewer interest pixels than rays per batch)",
@@ -186,7 +190,9 @@ def main():
     ap.add_argument("--iters", type=int, default=ITERS)
     ap.add_argument("--epochs", type=int, default=EPOCHS)
     ap.add_argument("--limit", type=int, default=300, help="seconds a group may take")
-    ap.add_argument("--filter-sampling", choices=("dense", "occupied"), default="dense", help="NativePoseFilter's sampling in the filter group")
+    ap.add_argument("--filter-sampling", choices=("dense", "occupied", "resampled"), default="dense", help="NativePoseFilter's sampling in the filter group")
+    ap.add_argument("--filter-num-steps", type=int, default=128, help="coarse samples per ray of --filter-sampling resampled")
+    ap.add_argument("--filter-upsample-steps", type=int, default=128, help="importance samples per ray of --filter-sampling resampled")
     args = ap.parse_args()
     if args.phase:
         dev = torch.device("cuda:0")
@@ -196,7 +202,8 @@ def main():
     summary = {}
     for group in GROUPS:
         cmd = ["timeout", "-k", "10", str(args.limit), sys.executable, os.path.abspath(__file__), "--phase", group, "--rounds", str(args.rounds), "--side",
-               str(args.side), "--iters", str(args.iters), "--epochs", str(args.epochs), "--filter-sampling", args.filter_sampling]
+               str(args.side), "--iters", str(args.iters), "--epochs", str(args.epochs), "--filter-sampling", args.filter_sampling,
+               "--filter-num-steps", str(args.filter_num_steps), "--filter-upsample-steps", str(args.filter_upsample_steps)]
         done = subprocess.run(cmd, stdout=subprocess.PIPE, text=True)
         sys.stdout.write(done.stdout)
         sys.stdout.flush()
