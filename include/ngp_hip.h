@@ -462,7 +462,8 @@ int ngp_field_train_live_list(void* workspace, uint32_t M, const uint32_t** list
  * workspace: ngp_render_frame_workspace(N) bytes; at least 256 (NGP_EINVAL below that).  A caller that passes less than the full size gets the same
  * frame by a slower route: without the tile order below 256 + 48 KiB + 8 bytes per 64 rays, without the coarse occupancy map below 256 + C * Hgrid^3 / 512.
  * Hgrid (and H of ngp_march_rays / ngp_march_rays_train): a power of two, NGP_EINVAL otherwise (cells are addressed by Morton index, which for
- * any other size runs beyond the bitfield's C * H^3 bits). */
+ * any other size runs beyond the bitfield's C * H^3 bits).
+ * ngp_render_frame* and ngp_nav_render_frame* also refuse (NGP_EINVAL) a grid whose C * Hgrid^3 bits are not whole bytes (Hgrid = 1 with C not a multiple of 8). */
 size_t ngp_render_frame_workspace(uint32_t N);
 /* Validation switch, process-wide, default 1: ngp_render_frame jumps through empty 4^3 / 16^3 blocks of the occupancy
  * grid when that provably visits the reference's samples (render_fused.hip, rv_probe).  0 = march cell by cell like

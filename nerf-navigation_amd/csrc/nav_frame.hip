@@ -320,6 +320,8 @@ static int nvf_render_frame(const char* who, const ngp_nav_field_t* field_host, 
     // cells are addressed by Morton index: for a grid size that is not a power of two the index of a cell can lie beyond the end of the bitfield
     NGP_REQUIRE((Hgrid & (Hgrid - 1u)) == 0u, "%s: the grid size must be a power of two (cells are addressed by Morton index)", who);
     NGP_REQUIRE((uint64_t)C * Hgrid * Hgrid * Hgrid <= (1ull << 30), "%s: the occupancy grid has more than 2^30 cells", who);
+    // the bitfield is C * H^3 / 8 bytes: a grid of fewer bits than a byte holds (H = 1, C not a multiple of 8) has no whole number of them
+    NGP_REQUIRE(((uint64_t)C * Hgrid * Hgrid * Hgrid) % 8u == 0u, "%s: the occupancy grid's C * H^3 bits are not a whole number of bytes", who);
     NGP_REQUIRE(N <= 0xFFF00000u, "%s: too many rays", who);            // the queue's head runs past N by at most 64 per wave
     const nvf_ws ws = nvf_layout(N, workspace);
     if (workspace_bytes < ws.total)

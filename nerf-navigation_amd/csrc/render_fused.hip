@@ -955,6 +955,8 @@ static int rv_render_frame(const ngp_field_t* field_host, const float* rays_o, c
     // cells are addressed by Morton index: for a grid size that is not a power of two the index of a cell can lie beyond H^3 (H = 48: cell (47, 47, 47) has
     // index 2^18 - 1 > 48^3), i.e. beyond the end of the bitfield
     NGP_REQUIRE(rv_pow2(Hgrid), "render_frame: the grid size must be a power of two (cells are addressed by Morton index)");
+    // the bitfield is C * H^3 / 8 bytes: a grid of fewer bits than a byte holds (H = 1, C not a multiple of 8) has no whole number of them
+    NGP_REQUIRE(((uint64_t)C * Hgrid * Hgrid * Hgrid) % 8u == 0u, "render_frame: the occupancy grid's C * H^3 bits are not a whole number of bytes");
     hipStream_t s = (hipStream_t)stream;
     if (hipMemsetAsync(stats, 0, 4 * sizeof(uint32_t), s) != hipSuccess || hipMemsetAsync(ws.header, 0, RV_WS_HEADER_WORDS * 4, s) != hipSuccess)
         return ngp_fail(NGP_ELAUNCH, "render_frame: memset failed");

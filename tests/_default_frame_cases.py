@@ -122,6 +122,49 @@ CONDITIONED = ("two_cascades", "one_cascade", "dt_gamma_128", "dt_gamma_32", "sa
                "random_field_full_grid", "density_scale_2")
 
 
+# The frames tests/test_gpu_default_frame_inside.py renders from INSIDE the ring scene (tests/_frame_poses.py), 33 x 33 (direction components of exactly
+# 0.0) and 40 x 40 (8x8 tiles): field A from every pose at bound 2 (nested cascades) and 1.5 (not nested), from the centre at bound 3 (three cascades of
+# half-widths 1, 2, 3), and field B with density_scale 8 from inside a pillar and inside the slab (rays that saturate within their first few samples).
+INSIDE_SIZES = (33, 40)
+INSIDE_BOUNDS = (2.0, 1.5)
+
+
+def inside_name(pose, res, bound):
+    return f"inside_{pose}_{res}_bound_{bound:g}"
+
+
+def inside_sizes(pose, bound):
+    """the two sizes a pose is rendered at.  lintel_top at bound 2 takes 32 x 32 for its even size: at 40 x 40 one ray's float32 transmittance
+    crosses the 1e-4 stop one sample away from where the float64 field's does (tests/test_default_frame_host.py's condition on the inputs), so the
+    frame would measure the inputs' rounding, not a kernel; 32 is a multiple of 8 as well and meets the condition."""
+    return (33, 32) if (pose, bound) == ("lintel_top", 2.0) else INSIDE_SIZES
+
+
+def _register_inside():
+    import _frame_poses as FP
+    names, empty = [], []
+    for bound in INSIDE_BOUNDS:
+        for pose in FP.NAMES:
+            for res in inside_sizes(pose, bound):
+                name = inside_name(pose, res, bound)
+                CASES[name] = lambda pose=pose, res=res, bound=bound: _case("A", bound, _inside(pose, res), image_width=res)
+                names.append(name)
+                if pose in FP.NO_SAMPLES:
+                    empty.append(name)
+    CASES["inside_three_cascades"] = lambda: _case("A", 3.0, _inside("centre", 33), image_width=33)
+    names.append("inside_three_cascades")
+    for pose in ("in_solid", "slab_skim"):
+        for res in INSIDE_SIZES:
+            name = f"inside_{pose}_{res}_random_field_scale_8"
+            CASES[name] = lambda pose=pose, res=res: _case("B", 2.0, _inside(pose, res), density_scale=8.0, image_width=res)
+            names.append(name)
+    return tuple(names), tuple(empty)
+
+
+# CONDITIONED_INSIDE: held to the host test's bar like CONDITIONED; INSIDE_NO_SAMPLES: those of them whose frame has no sample at all (FP.NO_SAMPLES)
+CONDITIONED_INSIDE, INSIDE_NO_SAMPLES = _register_inside()
+
+
 def occupancy(case, oracle):
     """(grid or None, bitfield uint8 numpy, cascades) of a case; grid None = every bit set"""
     from ngp import workload as W

@@ -71,7 +71,10 @@ def constant_field(xyzs, dirs):
     return np.full(n, DENSITY, np.float32), np.full((n, 3), 0.5, np.float32)
 
 
+@functools.lru_cache(maxsize=None)
 def reference_constant(name, res, bound, min_near=0.2, dt_gamma=0.0):
+    """the constant field's reference does not depend on which kernel is tested: computed once per process and shared by the GPU files that render
+    these poses (the key is the call as written: pass min_near and dt_gamma by keyword; do not write to the result)"""
     from oracle import render_oracle as R
     o, d = rays(name, res)
     bitfield, cascade = scene(bound)

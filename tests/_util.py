@@ -19,6 +19,29 @@ def blob_bitfield(oracle, cascade=2, H=128, seed=0, n_blobs=40, bound=2.0):
     return oracle.packbits(grid, 0.5), grid
 
 
+def blob_bitfield_boxed(oracle, cascade=2, H=128, seed=0, n_blobs=40, bound=2.0):
+    """blob_bitfield's bitfield (the same spheres from the same draws, the same float32 arithmetic per cell) for grids too large to test every cell
+    against every sphere (256^3: 45 s there, 1 s here): a sphere is tested on the cells of its bounding box, widened by a cell.  Returns the
+    bitfield only; callers assert that it equals blob_bitfield's at a size where both are cheap."""
+    rng = np.random.default_rng(seed)
+    grid = np.zeros((cascade, H ** 3), np.float32)
+    for cas in range(cascade):
+        b = min(2.0 ** cas, bound)
+        axis = ((np.arange(H, dtype=np.int32).astype(np.float32) + 0.5) / H * 2 - 1) * b          # a cell centre's coordinate, as blob_bitfield forms it
+        c = rng.uniform(-0.8 * b, 0.8 * b, size=(n_blobs, 3)).astype(np.float32)
+        r = rng.uniform(0.05 * b, 0.25 * b, size=n_blobs).astype(np.float32)
+        for k in range(n_blobs):
+            lo = [max(int(np.searchsorted(axis, c[k, a] - r[k])) - 1, 0) for a in range(3)]
+            hi = [min(int(np.searchsorted(axis, c[k, a] + r[k])) + 1, H) for a in range(3)]
+            sq = [(axis[lo[a]:hi[a]] - c[k, a]) ** 2 for a in range(3)]
+            d2 = (sq[0][:, None, None] + sq[1][None, :, None]) + sq[2][None, None, :]                # numpy's sum over three float32: left to right
+            x, y, z = np.nonzero(d2 < r[k] ** 2)
+            cells = np.stack([x + lo[0], y + lo[1], z + lo[2]], -1).astype(np.int32)
+            if cells.shape[0]:
+                grid[cas, oracle.morton3D(cells)] = 1.0
+    return oracle.packbits(grid, 0.5)
+
+
 def camera_rays(n_side=32, radius=3.0, seed=0, jitter=True):
     """Pinhole rays from a camera on an orbit looking at the origin; a few degenerate directions appended."""
     rng = np.random.default_rng(seed)
@@ -142,4 +165,48 @@ def render_frame(ren, o, d, width, *, tile_order=None, block_skip=None, occupied
     finally:
         for fn, value in previous:
             fn(value)
+    return dict(image=image, depth=depth, weights_sum=weights_sum, stats=stats), ws, rc
+
+
+NULL = object()                      # render_default_frame(bitfield=NULL): a null pointer, where None means the renderer's own bitfield
+
+
+def render_default_frame(ren, o, d, width, *, dt_gamma=0.0, min_near=None, max_steps=1024, bitfield=None, grid_size=None, workspace_bytes=None,
+                         bg=1.0, camera=None):
+    """ngp_nav_render_frame as NGPRenderer._render_default_frame calls it (the field struct and the prepared weights from the renderer's own holder),
+    through ctypes, with NaN-filled image / depth / weights_sum, stats of -1 and a 0xAB-filled workspace, so that a value the kernel did not write, or a
+    workspace word it relied on without writing it, shows.  `bitfield` replaces the renderer's (NULL: a null pointer), `workspace_bytes` the size
+    ngp_nav_render_frame_workspace asks for (the tensor is exactly that long), `min_near` and `grid_size` the renderer's; `bg` a number or three.
+    camera=(pose, intrinsics, H, W): ngp_nav_render_frame_camera instead, `o`, `d` and `width` unused (o gives the device).
+    Returns (outputs, workspace, return code); the outputs stay NaN / -1 when the call refuses."""
+    import ctypes
+
+    import ngp_hip as H
+    import torch
+    L = H.lib()
+    dev = o.device
+    N = o.shape[0] if camera is None else int(camera[2]) * int(camera[3])
+    image = torch.full((N, 3), float("nan"), device=dev)
+    depth = torch.full((N,), float("nan"), device=dev)
+    weights_sum = torch.full((N,), float("nan"), device=dev)
+    stats = torch.full((4,), -1, dtype=torch.int32, device=dev)
+    ws_bytes = int(L.ngp_nav_render_frame_workspace(N)) if workspace_bytes is None else int(workspace_bytes)
+    ws = torch.full((max(ws_bytes, 16),), 0xAB, dtype=torch.uint8, device=dev)
+    bg3 = (ctypes.c_float * 3)(*([float(bg)] * 3 if np.isscalar(bg) else [float(v) for v in bg]))
+    aabb = (ctypes.c_float * 6)(*ren._aabb_host())
+    bits = ren.density_bitfield if bitfield is None else bitfield
+    if bits is NULL:
+        bits = None
+    else:
+        assert bits.dtype == torch.uint8 and bits.is_contiguous()
+    with torch.cuda.device(dev):
+        st, prep = ren._default_frame_field("render_default_frame").struct()
+        tail = (aabb, ren.min_near if min_near is None else float(min_near), H.ptr(bits), ren.cascade, ren.grid_size if grid_size is None else int(grid_size),
+                float(dt_gamma), int(max_steps), bg3, H.ptr(image), H.ptr(depth), H.ptr(weights_sum), H.ptr(stats), H.ptr(ws), ws_bytes, H.stream())
+        if camera is None:
+            rc = L.ngp_nav_render_frame(ctypes.byref(st), H.ptr(prep), H.ptr(o), H.ptr(d), N, int(width), *tail)
+        else:
+            pose_h, intr_h = H.camera_args(camera[0], camera[1])
+            rc = L.ngp_nav_render_frame_camera(ctypes.byref(st), H.ptr(prep), pose_h, intr_h, int(camera[2]), int(camera[3]), *tail)
+        torch.cuda.synchronize()
     return dict(image=image, depth=depth, weights_sum=weights_sum, stats=stats), ws, rc

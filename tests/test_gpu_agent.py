@@ -223,6 +223,57 @@ def test_frame_route_is_the_sensor_of_render_fused_over_the_agents_rays(queries,
     nav.NativeAgent(agent_cfg_of(start12(dev)), queries, sensor=queries.renderer)           # the queries' own renderer is sensor=None
 
 
+def state_at(pose):
+    """the state whose sensor camera is `pose` (camera-to-world, +z forward): the inverse of ngp_filter_pose.h's chain P = cycle (rot_x(pi/2) R)
+    diag(1, -1, -1), T = cycle position, with R = exp of the state's rotation vector.  Velocities are zero."""
+    P, T = np.asarray(pose, np.float64)[:3, :3], np.asarray(pose, np.float64)[:3, 3]
+    flip = np.diag([1.0, -1.0, -1.0])
+    Rb = np.stack([P[2] @ flip, P[0] @ flip, P[1] @ flip])                  # P[i] = Rb[(i + 1) % 3] diag(1, -1, -1)
+    R = np.stack([Rb[0], Rb[2], -Rb[1]])                                    # Rb = rot_x(pi / 2) R: rows R0, -R2, R1
+    assert abs(np.linalg.det(R) - 1.0) < 1e-6
+    angle = float(np.arccos(np.clip((np.trace(R) - 1.0) / 2.0, -1.0, 1.0)))
+    if np.sin(angle) > 1e-6:
+        axis = np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]]) / (2.0 * np.sin(angle))
+    else:                                                                   # a half turn: R = 2 a a^T - I
+        k = int(np.argmax(np.diag(R)))
+        axis = (R[k] + np.eye(3)[k]) / np.sqrt(2.0 * (R[k, k] + 1.0))
+    state = np.zeros(12, np.float32)
+    state[[1, 2, 0]] = T                                                    # T[i] = state[(i + 1) % 3]
+    state[6:9] = angle * axis
+    return state
+
+
+@pytest.mark.parametrize("name", ["centre", "in_solid"])
+def test_the_sensor_sees_the_scene_from_inside_it(queries, oracle, dev, name):
+    """The navigation loop's sensor renders from the vehicle's own pose, among the obstacles.  A sensor over the ring scene (field A of
+    tests/_default_frame_cases.py), the vehicle at the scene's centre and inside a pillar (tests/_frame_poses.py): the observation is bit for bit the
+    sensor's 8-bit round trip of render_fused over ngp_agent_rays' rays, and that frame is within test_gpu_default_frame.check's bars of the CPU
+    oracle's march along the same rays."""
+    import _default_frame_cases as DC
+    import _frame_poses as FP
+    from ngp import nav
+    from ngp import workload as Wl
+    from oracle import render_oracle as R
+    from test_gpu_default_frame import check, renderer
+    ren = renderer(dev, oracle, DC._case("A", 2.0, None))
+    agent = nav.NativeAgent(agent_cfg_of(start12(dev)), queries, sensor=ren)
+    _, state, img = agent.state2image(torch.from_numpy(state_at(FP.pose(name))))
+    rays_o, rays_d = agent.rays(state)
+    o, d = rays_o.cpu().numpy(), rays_d.cpu().numpy()
+    want_o, want_d = Wl.get_rays(FP.pose(name), [float(v) for v in queries.intrinsics], H, W)
+    assert np.array_equal(o, want_o) and float(np.max(np.abs(d - want_d))) < 1e-5, "the sensor's camera is not where the pose puts it"
+    out = ren.render_fused(rays_o, rays_d, image_width=W, bg_color=1)
+    assert torch.equal(agent.render(rays_o, rays_d), out["image"])
+    png, target = AC.sensor_restated(out["image"].cpu().numpy())
+    assert np.array_equal(img.cpu().numpy(), png.reshape(H, W, 3))
+    assert np.array_equal(agent.target.cpu().numpy().view(np.uint32), target.reshape(H, W, 3).view(np.uint32))
+    assert len(torch.unique(img)) > 8
+    ref = R.render_single_march(DC.field_fn(DC.oracle_field("A", 2.0)), o, d, FP.scene(2.0)[0], 2.0, 2)
+    assert ref["samples"] > 1000 and 0 < int((ref["consumed"] > 0).sum())
+    stats = check(out, ref, DC._case("A", 2.0, (o, d), image_width=W), oracle, f"sensor from {name}")
+    assert int(stats[1]) == 0
+
+
 @pytest.mark.parametrize("route", ["render_fn", "frame"])
 def test_step_returns_before_the_device_has_run_it(queries, dev, route):
     """a step queued behind a long-running kernel returns while that kernel is still running: it waits for nothing on the device"""
