@@ -19,6 +19,10 @@
 //                              list of its occupied samples: the pose filter's opt-in route (the section before "host side" below)
 //   k_nav_resample, k_sample_pdf, k_nav_run_fwd<true> / _bwd<true>   the run with upsample_steps > 0: the coarse pass, sample_pdf's inverse CDF and the depth-ordered
 //                              merge in one launch, then the run kernels over that explicit depth list ("The resampled run" below)
+// The run exists ONCE: nv_run_sample_fwd<W, COLOUR> and nv_run_sample_bwd<W> are one sample's forward and backward on one of the W lanes that share its
+// ray (W = NV_BLOCK: the dense / depth-list kernels and the resample kernel's coarse pass; W = 64: the occupied kernels), over the team primitives
+// nv_team_excl_product / _sum / _excl_suffix_sum<W>, with nv_ray_load, nv_run_write and nv_run_write_grads around them.  A kernel states which sample
+// a lane handles and where its record lies, its LDS carve-up, and what is its own (the lattice walk and compaction; the pdf, inverse CDF and merge).
 // float32 FMA throughput is the same on the VALU and on the f32 MFMA of this chip, and the batch is small (10 k - 524 k points), so
 // the matrix cores would buy nothing here; what the fusion removes is launches and the [M, 64] round trips through HBM.
 //
@@ -230,23 +234,31 @@ __device__ __forceinline__ float nv_clip_pass(float x, float lo, float hi) {
     return a * b;
 }
 
+struct nv_ray { float ox, oy, oz, dx, dy, dz, near, far, span; };
+
+__device__ __forceinline__ nv_ray nv_ray_load(const nav_run& R, uint32_t n) {
+    nv_ray r;
+    r.ox = R.rays_o[3ull * n]; r.oy = R.rays_o[3ull * n + 1]; r.oz = R.rays_o[3ull * n + 2];
+    r.dx = R.rays_d[3ull * n]; r.dy = R.rays_d[3ull * n + 1]; r.dz = R.rays_d[3ull * n + 2];
+    r.near = R.nears[n]; r.far = R.fars[n]; r.span = r.far - r.near;
+    return r;
+}
+
 // AT: the depths come from the ray's row of the depth list (`zrow`, T entries) instead of the linspace lattice, and the last delta is (far - near) / dist
 template <bool AT = false>
-__device__ __forceinline__ nv_sample nv_sample_at(const nav_run& R, uint32_t i, float near, float far, float ox, float oy, float oz,
-                                                  float dx, float dy, float dz, const float* __restrict__ zrow = nullptr, uint32_t dist = 0) {
+__device__ __forceinline__ nv_sample nv_sample_at(const nav_run& R, uint32_t i, const nv_ray& ray, const float* __restrict__ zrow = nullptr, uint32_t dist = 0) {
     nv_sample s;
-    const float span = far - near;
     if (AT) {
         s.lin = 0.0f;
         s.z = zrow[i];                                                   // the merged list (:196-197)
-        s.znext_minus_z = (i + 1 < R.T) ? zrow[i + 1] - s.z : span / (float)dist;        // :206-207 with :153's sample_dist
+        s.znext_minus_z = (i + 1 < R.T) ? zrow[i + 1] - s.z : ray.span / (float)dist;    // :206-207 with :153's sample_dist
     } else {
         s.lin = nv_lin(i, R.T);
-        s.z = near + span * s.lin;                                       // :147-148
-        const float zn = (i + 1 < R.T) ? near + span * nv_lin(i + 1, R.T) : 0.0f;
-        s.znext_minus_z = (i + 1 < R.T) ? zn - s.z : span / (float)R.T;  // deltas, last = sample_dist (:206-207, :151)
+        s.z = ray.near + ray.span * s.lin;                               // :147-148
+        const float zn = (i + 1 < R.T) ? ray.near + ray.span * nv_lin(i + 1, R.T) : 0.0f;
+        s.znext_minus_z = (i + 1 < R.T) ? zn - s.z : ray.span / (float)R.T;              // deltas, last = sample_dist (:206-207, :151)
     }
-    const float x = ox + dx * s.z, y = oy + dy * s.z, z = oz + dz * s.z; // :158
+    const float x = ray.ox + ray.dx * s.z, y = ray.oy + ray.dy * s.z, z = ray.oz + ray.dz * s.z;     // :158
     s.px = fminf(fmaxf(x, R.aabb[0]), R.aabb[3]);                        // :159
     s.py = fminf(fmaxf(y, R.aabb[1]), R.aabb[4]);
     s.pz = fminf(fmaxf(z, R.aabb[2]), R.aabb[5]);
@@ -256,12 +268,44 @@ __device__ __forceinline__ nv_sample nv_sample_at(const nav_run& R, uint32_t i, 
     return s;
 }
 
-// exclusive prefix product of one value per thread over the block (256 threads = 4 waves); `total` = the product of all of them
-__device__ __forceinline__ float nv_block_excl_product(float v, float* __restrict__ lds4, float& total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    float incl = v;
+// ---- team primitives: one value per lane over the W lanes that share a ray.  W = NV_BLOCK: the four waves of a workgroup meet through `lds4` (two
+// barriers per call); W = 64: one wave, shuffles only, no barrier, `lds4` untouched.  Two specialisations of one name, chosen at compile time. ----
+
+__device__ __forceinline__ float nro_wave_sum(float v) {                // lane 0 holds the sum
     #pragma unroll
-    for (int off = 1; off < 64; off <<= 1) { const float up = __shfl_up(incl, off, 64); if (lane >= off) incl = up * incl; }
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    return v;
+}
+
+__device__ __forceinline__ float nv_wave_incl_product(float v) {
+    const int lane = threadIdx.x & 63;
+    #pragma unroll
+    for (int off = 1; off < 64; off <<= 1) { const float up = __shfl_up(v, off, 64); if (lane >= off) v = up * v; }
+    return v;
+}
+
+// EXCLUSIVE by construction (scan of the sequence shifted by one lane): an inclusive scan minus the own term would cancel --
+// an opaque sample's own A w is many orders of magnitude above the sum of everything behind it, and that small sum, divided
+// by the sample's equally small (1 - alpha), is a first-order term of d L / d alpha
+__device__ __forceinline__ float nv_wave_excl_suffix_sum(float v) {
+    const int lane = threadIdx.x & 63;
+    float rs = __shfl_down(v, 1, 64);
+    if (lane == 63) rs = 0.0f;
+    #pragma unroll
+    for (int off = 1; off < 64; off <<= 1) { const float dn = __shfl_down(rs, off, 64); if (lane + off < 64) rs += dn; }
+    return rs;
+}
+
+// exclusive prefix product of one value per lane; `total` = the product of all of them
+template <uint32_t W> __device__ __forceinline__ float nv_team_excl_product(float v, float* __restrict__ lds4, float& total);
+// the sum of one value per lane (W = 64: in lane 0)
+template <uint32_t W> __device__ __forceinline__ float nv_team_sum(float v, float* __restrict__ lds4);
+// `behind` + the sum of the lanes after this one; `total` = the sum of all lanes
+template <uint32_t W> __device__ __forceinline__ float nv_team_excl_suffix_sum(float v, float behind, float* __restrict__ lds4, float& total);
+
+template <> __device__ __forceinline__ float nv_team_excl_product<NV_BLOCK>(float v, float* __restrict__ lds4, float& total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const float incl = nv_wave_incl_product(v);
     __syncthreads();
     if (lane == 63) lds4[wave] = incl;
     __syncthreads();
@@ -274,13 +318,41 @@ __device__ __forceinline__ float nv_block_excl_product(float v, float* __restric
     return base * before;
 }
 
-__device__ __forceinline__ float nv_block_sum(float v, float* __restrict__ lds4) {
-    #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+template <> __device__ __forceinline__ float nv_team_excl_product<64>(float v, float* __restrict__, float& total) {
+    const float incl = nv_wave_incl_product(v);
+    float before = __shfl_up(incl, 1, 64);
+    if ((threadIdx.x & 63) == 0) before = 1.0f;
+    total = __shfl(incl, 63, 64);
+    return before;
+}
+
+template <> __device__ __forceinline__ float nv_team_sum<NV_BLOCK>(float v, float* __restrict__ lds4) {
+    v = nro_wave_sum(v);
     __syncthreads();
     if ((threadIdx.x & 63) == 0) lds4[threadIdx.x >> 6] = v;
     __syncthreads();
     return (lds4[0] + lds4[1]) + (lds4[2] + lds4[3]);
+}
+
+template <> __device__ __forceinline__ float nv_team_sum<64>(float v, float* __restrict__) { return nro_wave_sum(v); }
+
+template <> __device__ __forceinline__ float nv_team_excl_suffix_sum<NV_BLOCK>(float v, float behind, float* __restrict__ lds4, float& total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const float rs = nv_wave_excl_suffix_sum(v);
+    __syncthreads();
+    if (lane == 0) lds4[wave] = rs + v;                                  // the wave's total
+    __syncthreads();
+    float tot = 0.0f;
+    #pragma unroll
+    for (int wv = (int)(NV_BLOCK / 64) - 1; wv >= 0; wv--) { const float t = lds4[wv]; if (wv > wave) behind += t; tot += t; }
+    total = tot;
+    return behind + rs;
+}
+
+template <> __device__ __forceinline__ float nv_team_excl_suffix_sum<64>(float v, float behind, float* __restrict__, float& total) {
+    const float rs = nv_wave_excl_suffix_sum(v);
+    total = __shfl(rs + v, 0, 64);
+    return behind + rs;
 }
 
 // alpha and the transmittance factor of one sample (:208-209); ex = exp(-delta scale sigma), the number alpha was rounded from
@@ -299,38 +371,39 @@ static constexpr uint32_t NV_REC_WORDS = 27;
 // 2^-25, which for an opaque sample (ex = 1e-4) is 3e-4 of d alpha / d sigma = delta scale ex, and that sample is the one the ray's gradient hangs on
 enum { NV_R_OUT = 0, NV_R_RELU = 16, NV_R_EX = 18, NV_R_TR = 19, NV_R_RGB = 20, NV_R_MA = 23, NV_R_MB = 25 };
 
-template <bool AT>
-__global__ __launch_bounds__(NV_BLOCK) void k_nav_run_fwd(nav_params P, nav_run R, float* __restrict__ image, float* __restrict__ depth,
-                                                          float* __restrict__ weights_sum, uint32_t* __restrict__ save, nav_at Z) {
-    extern __shared__ float nv_smem[];
-    float* lds4 = nv_smem;                                              // 16 floats of scan scratch
-    float* col = nv_smem + 16 + threadIdx.x;                            // this lane's column of the [64][256] scratch
-    const uint32_t n = blockIdx.x;
-    const size_t NT = (size_t)R.N * R.T;
-    const float ox = R.rays_o[3ull * n], oy = R.rays_o[3ull * n + 1], oz = R.rays_o[3ull * n + 2];
-    const float dx = R.rays_d[3ull * n], dy = R.rays_d[3ull * n + 1], dz = R.rays_d[3ull * n + 2];
-    const float near = R.nears[n], far = R.fars[n], span = far - near;
-    const float* zrow = AT ? Z.z + (size_t)n * R.T : nullptr;
-    float carry = 1.0f, acc_w = 0.0f, acc_d = 0.0f, acc_r = 0.0f, acc_g = 0.0f, acc_b = 0.0f;
-    for (uint32_t c0 = 0; c0 < R.T; c0 += NV_BLOCK) {
-        const uint32_t i = c0 + threadIdx.x;
-        const bool live = i < R.T;
-        const nv_sample s = nv_sample_at<AT>(R, live ? i : R.T - 1, near, far, ox, oy, oz, dx, dy, dz, zrow, Z.dist);
-        float x0, x1, x2;
-        const bool inside = nv_normalise(P, s.px, s.py, s.pz, x0, x1, x2);
-        float out[16];
-        const uint64_t relu = nv_density_forward<NV_RUN_U>(P, inside, x0, x1, x2, col, out);
-        float ex, alpha, keep;
-        nv_alpha(s.znext_minus_z, P.density_scale, expf(out[0]), ex, alpha, keep);
-        if (!live) { alpha = 0.0f; keep = 1.0f; }
-        float total;
-        const float Tr = carry * nv_block_excl_product(keep, lds4, total);
-        const float w = alpha * Tr;
-        uint32_t* q = save + (size_t)n * R.T + i;
+// a 64-bit mask in two words of the record `q` (word stride NT)
+__device__ __forceinline__ void nv_rec_put64(uint32_t* __restrict__ q, uint32_t word, size_t NT, uint64_t m) {
+    q[word * NT] = (uint32_t)m; q[(word + 1) * NT] = (uint32_t)(m >> 32);
+}
+__device__ __forceinline__ uint64_t nv_rec_get64(const uint32_t* __restrict__ q, uint32_t word, size_t NT) {
+    return (uint64_t)q[word * NT] | ((uint64_t)q[(word + 1) * NT] << 32);
+}
+
+struct nv_run_sums { float w, d, r, g, b; };                            // a lane's share of weights_sum, depth and the colour
+
+// One sample of the run, forward, on one of the W lanes of its ray: density, alpha, the weight w = alpha T (returned) with the transmittance T = `carry` x
+// the exclusive product over the lanes in front (nerf/renderer.py:206-210); `carry` moves on to the next chunk.  COLOUR: the record into word-major
+// `save` at `at` (save null: nothing is kept), the colour net where the weight matters, and the lane's sums; without it the function ends at the weight.
+// A lane that is not `live` computes along (the scans need every lane) and contributes alpha = 0, keep = 1: exact no-ops.
+template <uint32_t W, bool COLOUR>
+__device__ __forceinline__ float nv_run_sample_fwd(const nav_params& P, const nv_ray& ray, const nv_sample& s, bool live, float& carry, float* __restrict__ col,
+                                                   float* __restrict__ lds4, uint32_t* __restrict__ save, size_t at, size_t NT, nv_run_sums& acc) {
+    float x0, x1, x2;
+    const bool inside = nv_normalise(P, s.px, s.py, s.pz, x0, x1, x2);
+    float out[16];
+    const uint64_t relu = nv_density_forward<NV_RUN_U, W>(P, inside, x0, x1, x2, col, out);
+    float ex, alpha, keep;
+    nv_alpha(s.znext_minus_z, P.density_scale, expf(out[0]), ex, alpha, keep);
+    if (!live) { alpha = 0.0f; keep = 1.0f; }
+    float total;
+    const float Tr = carry * nv_team_excl_product<W>(keep, lds4, total);
+    const float w = alpha * Tr;
+    if (COLOUR) {
+        uint32_t* q = save + at;
         if (save && live) {                                              // before the colour net, so that out[] dies here
             #pragma unroll
             for (int m = 0; m < 16; m++) q[(NV_R_OUT + m) * NT] = __float_as_uint(out[m]);
-            q[NV_R_RELU * NT] = (uint32_t)relu; q[(NV_R_RELU + 1) * NT] = (uint32_t)(relu >> 32);
+            nv_rec_put64(q, NV_R_RELU, NT, relu);
             q[NV_R_EX * NT] = __float_as_uint(ex); q[NV_R_TR * NT] = __float_as_uint(Tr);
         }
         float rgb[3] = {0.0f, 0.0f, 0.0f};
@@ -339,23 +412,30 @@ __global__ __launch_bounds__(NV_BLOCK) void k_nav_run_fwd(nav_params P, nav_run 
             float geo[NV_GEO];
             #pragma unroll
             for (int m = 0; m < NV_GEO; m++) geo[m] = out[1 + m];
-            nv_color_forward(P, dx, dy, dz, geo, col, rgb, ma, mb);
+            nv_color_forward<W>(P, ray.dx, ray.dy, ray.dz, geo, col, rgb, ma, mb);
         }
         if (save && live) {
             q[NV_R_RGB * NT] = __float_as_uint(rgb[0]); q[(NV_R_RGB + 1) * NT] = __float_as_uint(rgb[1]); q[(NV_R_RGB + 2) * NT] = __float_as_uint(rgb[2]);
-            q[NV_R_MA * NT] = (uint32_t)ma; q[(NV_R_MA + 1) * NT] = (uint32_t)(ma >> 32);
-            q[NV_R_MB * NT] = (uint32_t)mb; q[(NV_R_MB + 1) * NT] = (uint32_t)(mb >> 32);
+            nv_rec_put64(q, NV_R_MA, NT, ma);
+            nv_rec_put64(q, NV_R_MB, NT, mb);
         }
-        const float oz01 = fminf(fmaxf((s.z - near) / span, 0.0f), 1.0f); // :225
-        acc_w += w; acc_d += w * oz01; acc_r += w * rgb[0]; acc_g += w * rgb[1]; acc_b += w * rgb[2];
-        carry *= total;
+        const float oz01 = fminf(fmaxf((s.z - ray.near) / ray.span, 0.0f), 1.0f);        // :225
+        acc.w += w; acc.d += w * oz01; acc.r += w * rgb[0]; acc.g += w * rgb[1]; acc.b += w * rgb[2];
     }
-    const float ws = nv_block_sum(acc_w, lds4), dsum = nv_block_sum(acc_d, lds4);
-    const float r = nv_block_sum(acc_r, lds4), g = nv_block_sum(acc_g, lds4), b = nv_block_sum(acc_b, lds4);
-    if (threadIdx.x == 0) {
+    carry *= total;
+    return w;
+}
+
+// the ray's weights_sum, depth and image from its lanes' sums (:241)
+template <uint32_t W>
+__device__ __forceinline__ void nv_run_write(const nav_run& R, uint32_t n, const nv_run_sums& acc, float* __restrict__ lds4, float* __restrict__ image,
+                                             float* __restrict__ depth, float* __restrict__ weights_sum) {
+    const float ws = nv_team_sum<W>(acc.w, lds4), dsum = nv_team_sum<W>(acc.d, lds4);
+    const float r = nv_team_sum<W>(acc.r, lds4), g = nv_team_sum<W>(acc.g, lds4), b = nv_team_sum<W>(acc.b, lds4);
+    if (threadIdx.x == 0) {                                              // a ray without a sample: ws = 0, so the image is bg bit for bit
         weights_sum[n] = ws;
         depth[n] = dsum;
-        image[3ull * n] = r + (1.0f - ws) * R.bg[0];                    // :241
+        image[3ull * n] = r + (1.0f - ws) * R.bg[0];
         image[3ull * n + 1] = g + (1.0f - ws) * R.bg[1];
         image[3ull * n + 2] = b + (1.0f - ws) * R.bg[2];
     }
@@ -389,6 +469,94 @@ __device__ __forceinline__ void nv_color_backward_saved(const nav_params& P, flo
     gdx += sx; gdy += sy; gdz += sz;
 }
 
+struct nv_run_gout { float i0, i1, i2, d, w; };                         // d L / d image, depth, weights_sum of the ray
+struct nv_ray_grads { float o0, o1, o2, dx, dy, dz; };                  // a lane's share of d L / d rays_o, d L / d rays_d
+
+__device__ __forceinline__ nv_run_gout nv_run_gout_load(uint32_t n, const float* __restrict__ gimage, const float* __restrict__ gdepth,
+                                                        const float* __restrict__ gws) {
+    return {gimage[3ull * n], gimage[3ull * n + 1], gimage[3ull * n + 2], gdepth ? gdepth[n] : 0.0f, gws ? gws[n] : 0.0f};
+}
+
+// One sample of the run, backward, from its record `q` (that of any sample of the ray for a lane that is not `live`).  The chunks run back to front:
+// d L / d sigma_i needs the sum over the samples BEHIND i, which `suffix` carries from chunk to chunk.
+template <uint32_t W>
+__device__ __forceinline__ void nv_run_sample_bwd(const nav_params& P, const nav_run& R, const nv_ray& ray, const nv_run_gout& g, const nv_sample& s, bool live,
+                                                  float& suffix, float* __restrict__ col, float* __restrict__ lds4, const uint32_t* __restrict__ q, size_t NT,
+                                                  nv_ray_grads& acc) {
+    const float ex = live ? __uint_as_float(q[NV_R_EX * NT]) : 1.0f, Tr = live ? __uint_as_float(q[NV_R_TR * NT]) : 0.0f;
+    const float alpha = 1.0f - ex;                                       // the forward's own alpha
+    const float rgb[3] = {__uint_as_float(q[NV_R_RGB * NT]), __uint_as_float(q[(NV_R_RGB + 1) * NT]), __uint_as_float(q[(NV_R_RGB + 2) * NT])};
+    const float w = alpha * Tr;
+    const bool masked = live && w > 1e-4f;
+    const float oz01 = fminf(fmaxf((s.z - ray.near) / ray.span, 0.0f), 1.0f);
+    // A_i = d L / d w_i : image (colour minus background), depth, weights_sum
+    const float A = live ? (g.i0 * (rgb[0] - R.bg[0]) + g.i1 * (rgb[1] - R.bg[1]) + g.i2 * (rgb[2] - R.bg[2]) + g.d * oz01 + g.w) : 0.0f;
+    float chunk_total;
+    const float S = nv_team_excl_suffix_sum<W>(A * w, suffix, lds4, chunk_total);        // sum over k > i of A_k w_k
+    suffix += chunk_total;
+    // w_i = alpha_i T_i, T_k (k > i) carries the factor (1 - alpha_i + eps):
+    //   d L / d alpha_i = A_i T_i - S_i / (1 - alpha_i + eps);   d alpha_i / d sigma_i = delta_i scale exp(-delta_i scale sigma_i)
+    // S_i / keep_i with the forward's own (rounded) keep: every T behind i carries that factor, so the quotient does not see its rounding
+    const float keep = 1.0f - alpha + 1e-15f;
+    const float gsigma = live ? s.znext_minus_z * P.density_scale * ex * (A * Tr - S / keep) : 0.0f;
+
+    float gout[16];
+    #pragma unroll
+    for (int m = 0; m < 16; m++) gout[m] = 0.0f;
+    if (masked) {
+        float ggeo[NV_GEO];
+        const uint64_t ma = nv_rec_get64(q, NV_R_MA, NT), mb = nv_rec_get64(q, NV_R_MB, NT);
+        const float grgb[3] = {g.i0 * w, g.i1 * w, g.i2 * w};
+        nv_color_backward_saved<W>(P, ray.dx, ray.dy, ray.dz, rgb, ma, mb, grgb, col, ggeo, acc.dx, acc.dy, acc.dz);
+        #pragma unroll
+        for (int m = 0; m < NV_GEO; m++) gout[1 + m] = ggeo[m];
+    }
+    gout[0] = gsigma * nv_exp_clamped(__uint_as_float(q[NV_R_OUT * NT]));
+    const uint64_t relu = nv_rec_get64(q, NV_R_RELU, NT);
+    float x0, x1, x2;
+    const bool inside = nv_normalise(P, s.px, s.py, s.pz, x0, x1, x2);
+    float gx, gy, gz;
+    nv_density_backward<NV_RUN_U, W>(P, inside, x0, x1, x2, relu, gout, col, gx, gy, gz);
+    if (!live) { gx = 0.0f; gy = 0.0f; gz = 0.0f; }
+    gx *= s.bx; gy *= s.by; gz *= s.bz;                                  // clipped coordinates pass no (or half the) gradient (:159)
+    acc.o0 += gx; acc.o1 += gy; acc.o2 += gz;
+    acc.dx = __builtin_fmaf(s.z, gx, acc.dx); acc.dy = __builtin_fmaf(s.z, gy, acc.dy); acc.dz = __builtin_fmaf(s.z, gz, acc.dz);
+}
+
+template <uint32_t W>
+__device__ __forceinline__ void nv_run_write_grads(uint32_t n, const nv_ray_grads& acc, float* __restrict__ lds4, float* __restrict__ grays_o,
+                                                   float* __restrict__ grays_d) {
+    const float a0 = nv_team_sum<W>(acc.o0, lds4), a1 = nv_team_sum<W>(acc.o1, lds4), a2 = nv_team_sum<W>(acc.o2, lds4);
+    const float b0 = nv_team_sum<W>(acc.dx, lds4), b1 = nv_team_sum<W>(acc.dy, lds4), b2 = nv_team_sum<W>(acc.dz, lds4);
+    if (threadIdx.x == 0) {                                              // a ray without a sample: exact zeros
+        grays_o[3ull * n] = a0; grays_o[3ull * n + 1] = a1; grays_o[3ull * n + 2] = a2;
+        grays_d[3ull * n] = b0; grays_d[3ull * n + 1] = b1; grays_d[3ull * n + 2] = b2;
+    }
+}
+
+// ---- the dense run and the run over a depth list: one 256-thread workgroup per ray, a lane's sample = its place in the lattice chunk ----
+
+template <bool AT>
+__global__ __launch_bounds__(NV_BLOCK) void k_nav_run_fwd(nav_params P, nav_run R, float* __restrict__ image, float* __restrict__ depth,
+                                                          float* __restrict__ weights_sum, uint32_t* __restrict__ save, nav_at Z) {
+    extern __shared__ float nv_smem[];
+    float* lds4 = nv_smem;                                              // 16 floats of scan scratch
+    float* col = nv_smem + 16 + threadIdx.x;                            // this lane's column of the [64][256] scratch
+    const uint32_t n = blockIdx.x;
+    const size_t NT = (size_t)R.N * R.T;
+    const nv_ray ray = nv_ray_load(R, n);
+    const float* zrow = AT ? Z.z + (size_t)n * R.T : nullptr;
+    float carry = 1.0f;
+    nv_run_sums acc = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    for (uint32_t c0 = 0; c0 < R.T; c0 += NV_BLOCK) {
+        const uint32_t i = c0 + threadIdx.x;
+        const bool live = i < R.T;
+        const nv_sample s = nv_sample_at<AT>(R, live ? i : R.T - 1, ray, zrow, Z.dist);
+        nv_run_sample_fwd<NV_BLOCK, true>(P, ray, s, live, carry, col, lds4, save, (size_t)n * R.T + i, NT, acc);
+    }
+    nv_run_write<NV_BLOCK>(R, n, acc, lds4, image, depth, weights_sum);
+}
+
 template <bool AT>
 __global__ __launch_bounds__(NV_BLOCK) void k_nav_run_bwd(nav_params P, nav_run R, const float* __restrict__ gimage, const float* __restrict__ gdepth,
                                                           const float* __restrict__ gws, const uint32_t* __restrict__ save,
@@ -398,98 +566,35 @@ __global__ __launch_bounds__(NV_BLOCK) void k_nav_run_bwd(nav_params P, nav_run 
     float* col = nv_smem + 16 + threadIdx.x;
     const uint32_t n = blockIdx.x;
     const size_t NT = (size_t)R.N * R.T;
-    const float ox = R.rays_o[3ull * n], oy = R.rays_o[3ull * n + 1], oz = R.rays_o[3ull * n + 2];
-    const float dx = R.rays_d[3ull * n], dy = R.rays_d[3ull * n + 1], dz = R.rays_d[3ull * n + 2];
-    const float near = R.nears[n], far = R.fars[n], span = far - near;
+    const nv_ray ray = nv_ray_load(R, n);
     const float* zrow = AT ? Z.z + (size_t)n * R.T : nullptr;
-    const float gi0 = gimage[3ull * n], gi1 = gimage[3ull * n + 1], gi2 = gimage[3ull * n + 2];
-    const float gd = gdepth ? gdepth[n] : 0.0f, gw = gws ? gws[n] : 0.0f;
+    const nv_run_gout g = nv_run_gout_load(n, gimage, gdepth, gws);
     const uint32_t nchunks = (R.T + NV_BLOCK - 1) / NV_BLOCK;
-
-    // back to front: d L / d sigma_i needs the sum over the samples BEHIND i, so the chunks run in reverse and carry that sum
     float suffix = 0.0f;
-    float go0 = 0.0f, go1 = 0.0f, go2 = 0.0f, gdx = 0.0f, gdy = 0.0f, gdz = 0.0f;
+    nv_ray_grads acc = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
     for (uint32_t cc = nchunks; cc-- > 0;) {
         const uint32_t i = cc * NV_BLOCK + threadIdx.x;
         const bool live = i < R.T;
-        const nv_sample s = nv_sample_at<AT>(R, live ? i : R.T - 1, near, far, ox, oy, oz, dx, dy, dz, zrow, Z.dist);
-        const uint32_t* q = save + (size_t)n * R.T + (live ? i : R.T - 1);
-        const float ex = live ? __uint_as_float(q[NV_R_EX * NT]) : 1.0f, Tr = live ? __uint_as_float(q[NV_R_TR * NT]) : 0.0f;
-        const float alpha = 1.0f - ex;                                   // the forward's own alpha
-        const float rgb[3] = {__uint_as_float(q[NV_R_RGB * NT]), __uint_as_float(q[(NV_R_RGB + 1) * NT]), __uint_as_float(q[(NV_R_RGB + 2) * NT])};
-        const float w = alpha * Tr;
-        const bool masked = live && w > 1e-4f;
-        const float oz01 = fminf(fmaxf((s.z - near) / span, 0.0f), 1.0f);
-        // A_i = d L / d w_i : image (colour minus background), depth, weights_sum
-        const float A = live ? (gi0 * (rgb[0] - R.bg[0]) + gi1 * (rgb[1] - R.bg[1]) + gi2 * (rgb[2] - R.bg[2]) + gd * oz01 + gw) : 0.0f;
-        const float Aw = A * w;
-        // EXCLUSIVE by construction (scan of the sequence shifted by one lane): an inclusive scan minus the own term would cancel --
-        // an opaque sample's own A w is many orders of magnitude above the sum of everything behind it, and that small sum, divided
-        // by the sample's equally small (1 - alpha), is a first-order term of d L / d alpha
-        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-        float rs = __shfl_down(Aw, 1, 64);
-        if (lane == 63) rs = 0.0f;
-        #pragma unroll
-        for (int off = 1; off < 64; off <<= 1) { const float dn = __shfl_down(rs, off, 64); if (lane + off < 64) rs += dn; }
-        __syncthreads();
-        if (lane == 0) lds4[wave] = rs + Aw;                             // the wave's total
-        __syncthreads();
-        float behind = suffix, chunk_total = 0.0f;
-        #pragma unroll
-        for (int wv = (int)(NV_BLOCK / 64) - 1; wv >= 0; wv--) { const float t = lds4[wv]; if (wv > wave) behind += t; chunk_total += t; }
-        const float S = behind + rs;                                     // sum over k > i of A_k w_k
-        suffix += chunk_total;
-        // w_i = alpha_i T_i, T_k (k > i) carries the factor (1 - alpha_i + eps):
-        //   d L / d alpha_i = A_i T_i - S_i / (1 - alpha_i + eps);   d alpha_i / d sigma_i = delta_i scale exp(-delta_i scale sigma_i)
-        // S_i / keep_i with the forward's own (rounded) keep: every T behind i carries that factor, so the quotient does not see its rounding
-        const float keep = 1.0f - alpha + 1e-15f;
-        const float gsigma = live ? s.znext_minus_z * P.density_scale * ex * (A * Tr - S / keep) : 0.0f;
-
-        float gout[16];
-        #pragma unroll
-        for (int m = 0; m < 16; m++) gout[m] = 0.0f;
-        if (masked) {
-            float ggeo[NV_GEO];
-            const uint64_t ma = (uint64_t)q[NV_R_MA * NT] | ((uint64_t)q[(NV_R_MA + 1) * NT] << 32);
-            const uint64_t mb = (uint64_t)q[NV_R_MB * NT] | ((uint64_t)q[(NV_R_MB + 1) * NT] << 32);
-            const float grgb[3] = {gi0 * w, gi1 * w, gi2 * w};
-            nv_color_backward_saved(P, dx, dy, dz, rgb, ma, mb, grgb, col, ggeo, gdx, gdy, gdz);
-            #pragma unroll
-            for (int m = 0; m < NV_GEO; m++) gout[1 + m] = ggeo[m];
-        }
-        gout[0] = gsigma * nv_exp_clamped(__uint_as_float(q[NV_R_OUT * NT]));
-        const uint64_t relu = (uint64_t)q[NV_R_RELU * NT] | ((uint64_t)q[(NV_R_RELU + 1) * NT] << 32);
-        float x0, x1, x2;
-        const bool inside = nv_normalise(P, s.px, s.py, s.pz, x0, x1, x2);
-        float gx, gy, gz;
-        nv_density_backward<NV_RUN_U>(P, inside, x0, x1, x2, relu, gout, col, gx, gy, gz);
-        if (!live) { gx = 0.0f; gy = 0.0f; gz = 0.0f; }
-        gx *= s.bx; gy *= s.by; gz *= s.bz;                              // clipped coordinates pass no (or half the) gradient (:159)
-        go0 += gx; go1 += gy; go2 += gz;
-        gdx = __builtin_fmaf(s.z, gx, gdx); gdy = __builtin_fmaf(s.z, gy, gdy); gdz = __builtin_fmaf(s.z, gz, gdz);
+        const uint32_t ic = live ? i : R.T - 1;
+        const nv_sample s = nv_sample_at<AT>(R, ic, ray, zrow, Z.dist);
+        nv_run_sample_bwd<NV_BLOCK>(P, R, ray, g, s, live, suffix, col, lds4, save + (size_t)n * R.T + ic, NT, acc);
     }
-    const float a0 = nv_block_sum(go0, lds4), a1 = nv_block_sum(go1, lds4), a2 = nv_block_sum(go2, lds4);
-    const float b0 = nv_block_sum(gdx, lds4), b1 = nv_block_sum(gdy, lds4), b2 = nv_block_sum(gdz, lds4);
-    if (threadIdx.x == 0) {
-        grays_o[3ull * n] = a0; grays_o[3ull * n + 1] = a1; grays_o[3ull * n + 2] = a2;
-        grays_d[3ull * n] = b0; grays_d[3ull * n + 1] = b1; grays_d[3ull * n + 2] = b2;
-    }
+    nv_run_write_grads<NV_BLOCK>(n, acc, lds4, grays_o, grays_d);
 }
 
 // ---------------------------------------------------------------------------
 // The same run with the occupancy grid consulted (DESIGN.md §3.5 "Occupancy-masked pose filter"): the sigma of every lattice sample whose occupancy bit
 // is clear is zero.  Such a sample has alpha = 0 and keep = 1 - 0 + 1e-15f = 1.0f exactly, so it drops out of every sum and of the transmittance product
 // without a rounding, and the kernels below never evaluate the field there: per ray they walk the T lattice positions (one bitfield byte each), compact
-// the indices of the occupied ones in lattice order, and run k_nav_run_fwd / _bwd's per-sample code over that list only.  Everything else is the dense
+// the indices of the occupied ones in lattice order, and run nv_run_sample_fwd / _bwd over that list only.  Everything else is the dense
 // run's: nears, fars, nv_lin, the clipped positions, the deltas of the LATTICE (not merged over the gaps), the colour mask, depth and background.
 //
 // The bit of a sample is that of its clipped float32 position under the march's own cell arithmetic, ngp_point::at (ngp_march.h), through a view whose
 // "ray" is the position itself (origin = position, direction 0, parameter 0) and whose step is 0, which leaves the step's cascade out: level = mip of
 // the position alone.  The mask is a constant of the float32 position: no gradient flows through it.
 //
-// Shape: ONE WAVE PER RAY (workgroup = 64 lanes).  With ~45 live samples per ray three of k_nav_run_*'s four waves would idle; here the activation
-// scratch is [64][64] floats = 16 KB plus the list (T x 2 B <= 8 KB), the scans are shuffles only, and the single barrier (list written, list read)
-// is a wave barrier.  The helpers of ngp_nav_field.h take the column stride as a template parameter for this (S = 64).
+// Shape: ONE WAVE PER RAY (workgroup = 64 lanes, the W = 64 team).  With ~45 live samples per ray three of k_nav_run_*'s four waves would idle; here the
+// activation scratch is [64][64] floats = 16 KB plus the list (T x 2 B <= 8 KB), and the single barrier (list written, list read) is a wave barrier.
 // No atomics; a ray's outputs depend on nothing but the ray; two runs give the same bits.
 // ---------------------------------------------------------------------------
 static constexpr uint32_t NO_W = 64;                                     // lanes per ray = the chunk width of the compacted list
@@ -514,12 +619,6 @@ __device__ __forceinline__ bool nro_occupied(const nav_occ& G, float bound, floa
     return (G.bits[bit >> 3] >> (bit & 7u)) & 1u;
 }
 
-__device__ __forceinline__ float nro_wave_sum(float v) {                // nv_block_sum's wave part; lane 0 holds the sum
-    #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
-
 // what the forward leaves besides the records: the ray's count and its list, so that the backward walks the same samples.  Record j of ray n (the j-th
 // occupied sample) sits where the dense run keeps sample j: word-major at n T + j
 struct nro_kept { uint32_t* save; uint32_t* counts; uint16_t* lists; };
@@ -532,16 +631,14 @@ __global__ __launch_bounds__(NO_W) void k_nav_run_occ_fwd(nav_params P, nav_run 
     uint16_t* list = reinterpret_cast<uint16_t*>(nv_smem + NV_H * NO_W); // [T]
     const uint32_t n = blockIdx.x;
     const size_t NT = (size_t)R.N * R.T;
-    const float ox = R.rays_o[3ull * n], oy = R.rays_o[3ull * n + 1], oz = R.rays_o[3ull * n + 2];
-    const float dx = R.rays_d[3ull * n], dy = R.rays_d[3ull * n + 1], dz = R.rays_d[3ull * n + 2];
-    const float near = R.nears[n], far = R.fars[n], span = far - near;
+    const nv_ray ray = nv_ray_load(R, n);
 
     // ---- the lattice walk: position and one bitfield byte per sample; the occupied indices, in lattice order, by ballot and prefix count ----
     uint32_t count = 0;
     for (uint32_t c0 = 0; c0 < R.T; c0 += NO_W) {
         const uint32_t i = c0 + lane;
         const bool live = i < R.T;
-        const nv_sample s = nv_sample_at(R, live ? i : R.T - 1, near, far, ox, oy, oz, dx, dy, dz);
+        const nv_sample s = nv_sample_at(R, live ? i : R.T - 1, ray);
         const bool occ = live && nro_occupied(G, P.bound, s.px, s.py, s.pz);
         const unsigned long long m = __ballot(occ);
         if (occ) list[count + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = (uint16_t)i;       // < count + popc(m) <= T
@@ -549,60 +646,18 @@ __global__ __launch_bounds__(NO_W) void k_nav_run_occ_fwd(nav_params P, nav_run 
     }
     __syncthreads();                                                     // one wave: the list is written before it is read
 
-    float carry = 1.0f, acc_w = 0.0f, acc_d = 0.0f, acc_r = 0.0f, acc_g = 0.0f, acc_b = 0.0f;
-    for (uint32_t j0 = 0; j0 < count; j0 += NO_W) {
+    float carry = 1.0f;
+    nv_run_sums acc = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    for (uint32_t j0 = 0; j0 < count; j0 += NO_W) {                      // a lane's sample = entry j of the list
         const uint32_t j = j0 + lane;
         const bool live = j < count;
         const uint32_t i = list[live ? j : count - 1];
-        const nv_sample s = nv_sample_at(R, i, near, far, ox, oy, oz, dx, dy, dz);
-        float x0, x1, x2;
-        const bool inside = nv_normalise(P, s.px, s.py, s.pz, x0, x1, x2);
-        float out[16];
-        const uint64_t relu = nv_density_forward<NV_RUN_U, NO_W>(P, inside, x0, x1, x2, col, out);
-        float ex, alpha, keep;
-        nv_alpha(s.znext_minus_z, P.density_scale, expf(out[0]), ex, alpha, keep);
-        if (!live) { alpha = 0.0f; keep = 1.0f; }
-        float incl = keep;                                               // exclusive product over the wave, nv_block_excl_product's wave part
-        #pragma unroll
-        for (int off = 1; off < 64; off <<= 1) { const float up = __shfl_up(incl, off, 64); if ((int)lane >= off) incl = up * incl; }
-        float before = __shfl_up(incl, 1, 64);
-        if (lane == 0) before = 1.0f;
-        const float total = __shfl(incl, 63, 64);
-        const float Tr = carry * before;
-        const float w = alpha * Tr;
-        uint32_t* q = K.save + (size_t)n * R.T + j;
-        if (K.save && live) {
-            K.lists[(size_t)n * R.T + j] = (uint16_t)i;
-            #pragma unroll
-            for (int m = 0; m < 16; m++) q[(NV_R_OUT + m) * NT] = __float_as_uint(out[m]);
-            q[NV_R_RELU * NT] = (uint32_t)relu; q[(NV_R_RELU + 1) * NT] = (uint32_t)(relu >> 32);
-            q[NV_R_EX * NT] = __float_as_uint(ex); q[NV_R_TR * NT] = __float_as_uint(Tr);
-        }
-        float rgb[3] = {0.0f, 0.0f, 0.0f};
-        uint64_t ma = 0, mb = 0;
-        if (live && w > 1e-4f) {
-            float geo[NV_GEO];
-            #pragma unroll
-            for (int m = 0; m < NV_GEO; m++) geo[m] = out[1 + m];
-            nv_color_forward<NO_W>(P, dx, dy, dz, geo, col, rgb, ma, mb);
-        }
-        if (K.save && live) {
-            q[NV_R_RGB * NT] = __float_as_uint(rgb[0]); q[(NV_R_RGB + 1) * NT] = __float_as_uint(rgb[1]); q[(NV_R_RGB + 2) * NT] = __float_as_uint(rgb[2]);
-            q[NV_R_MA * NT] = (uint32_t)ma; q[(NV_R_MA + 1) * NT] = (uint32_t)(ma >> 32);
-            q[NV_R_MB * NT] = (uint32_t)mb; q[(NV_R_MB + 1) * NT] = (uint32_t)(mb >> 32);
-        }
-        const float oz01 = fminf(fmaxf((s.z - near) / span, 0.0f), 1.0f);
-        acc_w += w; acc_d += w * oz01; acc_r += w * rgb[0]; acc_g += w * rgb[1]; acc_b += w * rgb[2];
-        carry *= total;
+        const nv_sample s = nv_sample_at(R, i, ray);
+        if (K.save && live) K.lists[(size_t)n * R.T + j] = (uint16_t)i;
+        nv_run_sample_fwd<NO_W, true>(P, ray, s, live, carry, col, nullptr, K.save, (size_t)n * R.T + j, NT, acc);
     }
-    const float ws = nro_wave_sum(acc_w), dsum = nro_wave_sum(acc_d);
-    const float r = nro_wave_sum(acc_r), g = nro_wave_sum(acc_g), b = nro_wave_sum(acc_b);
-    if (lane == 0) {                                                     // an empty ray: ws = 0, so the image is bg bit for bit
-        weights_sum[n] = ws;
-        depth[n] = dsum;
-        image[3ull * n] = r + (1.0f - ws) * R.bg[0];
-        image[3ull * n + 1] = g + (1.0f - ws) * R.bg[1];
-        image[3ull * n + 2] = b + (1.0f - ws) * R.bg[2];
+    nv_run_write<NO_W>(R, n, acc, nullptr, image, depth, weights_sum);
+    if (lane == 0) {
         if (K.save) K.counts[n] = count;
         if (counts_out) counts_out[n] = count;
     }
@@ -616,80 +671,32 @@ __global__ __launch_bounds__(NO_W) void k_nav_run_occ_bwd(nav_params P, nav_run 
     float* col = nv_smem + lane;
     const uint32_t n = blockIdx.x;
     const size_t NT = (size_t)R.N * R.T;
-    const float ox = R.rays_o[3ull * n], oy = R.rays_o[3ull * n + 1], oz = R.rays_o[3ull * n + 2];
-    const float dx = R.rays_d[3ull * n], dy = R.rays_d[3ull * n + 1], dz = R.rays_d[3ull * n + 2];
-    const float near = R.nears[n], far = R.fars[n], span = far - near;
-    const float gi0 = gimage[3ull * n], gi1 = gimage[3ull * n + 1], gi2 = gimage[3ull * n + 2];
-    const float gd = gdepth ? gdepth[n] : 0.0f, gw = gws ? gws[n] : 0.0f;
+    const nv_ray ray = nv_ray_load(R, n);
+    const nv_run_gout g = nv_run_gout_load(n, gimage, gdepth, gws);
     const uint32_t stored = K.counts[n];
     const uint32_t count = stored < R.T ? stored : R.T;                  // the forward's own number; the clamp keeps a foreign buffer inside the ray's slice
     const uint32_t nchunks = (count + NO_W - 1) / NO_W;
     const uint16_t* list = K.lists + (size_t)n * R.T;
 
-    float suffix = 0.0f;                                                 // back to front, as k_nav_run_bwd: the sum over the samples behind
-    float go0 = 0.0f, go1 = 0.0f, go2 = 0.0f, gdx = 0.0f, gdy = 0.0f, gdz = 0.0f;
+    float suffix = 0.0f;                                                 // over the occupied samples behind; the others' w is zero
+    nv_ray_grads acc = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
     for (uint32_t cc = nchunks; cc-- > 0;) {
         const uint32_t j = cc * NO_W + lane;
         const bool live = j < count;
         const uint32_t jc = live ? j : count - 1;
         const uint32_t listed = list[jc];
         const uint32_t i = listed < R.T ? listed : R.T - 1;
-        const nv_sample s = nv_sample_at(R, i, near, far, ox, oy, oz, dx, dy, dz);
-        const uint32_t* q = K.save + (size_t)n * R.T + jc;
-        const float ex = live ? __uint_as_float(q[NV_R_EX * NT]) : 1.0f, Tr = live ? __uint_as_float(q[NV_R_TR * NT]) : 0.0f;
-        const float alpha = 1.0f - ex;
-        const float rgb[3] = {__uint_as_float(q[NV_R_RGB * NT]), __uint_as_float(q[(NV_R_RGB + 1) * NT]), __uint_as_float(q[(NV_R_RGB + 2) * NT])};
-        const float w = alpha * Tr;
-        const bool masked = live && w > 1e-4f;
-        const float oz01 = fminf(fmaxf((s.z - near) / span, 0.0f), 1.0f);
-        const float A = live ? (gi0 * (rgb[0] - R.bg[0]) + gi1 * (rgb[1] - R.bg[1]) + gi2 * (rgb[2] - R.bg[2]) + gd * oz01 + gw) : 0.0f;
-        const float Aw = A * w;
-        float rs = __shfl_down(Aw, 1, 64);                               // exclusive by construction (k_nav_run_bwd says why)
-        if (lane == 63) rs = 0.0f;
-        #pragma unroll
-        for (int off = 1; off < 64; off <<= 1) { const float dn = __shfl_down(rs, off, 64); if (lane + off < 64) rs += dn; }
-        const float chunk_total = __shfl(rs + Aw, 0, 64);
-        const float S = suffix + rs;                                     // sum over the occupied k > i of A_k w_k; the others' w is zero
-        suffix += chunk_total;
-        const float keep = 1.0f - alpha + 1e-15f;
-        const float gsigma = live ? s.znext_minus_z * P.density_scale * ex * (A * Tr - S / keep) : 0.0f;
-
-        float gout[16];
-        #pragma unroll
-        for (int m = 0; m < 16; m++) gout[m] = 0.0f;
-        if (masked) {
-            float ggeo[NV_GEO];
-            const uint64_t ma = (uint64_t)q[NV_R_MA * NT] | ((uint64_t)q[(NV_R_MA + 1) * NT] << 32);
-            const uint64_t mb = (uint64_t)q[NV_R_MB * NT] | ((uint64_t)q[(NV_R_MB + 1) * NT] << 32);
-            const float grgb[3] = {gi0 * w, gi1 * w, gi2 * w};
-            nv_color_backward_saved<NO_W>(P, dx, dy, dz, rgb, ma, mb, grgb, col, ggeo, gdx, gdy, gdz);
-            #pragma unroll
-            for (int m = 0; m < NV_GEO; m++) gout[1 + m] = ggeo[m];
-        }
-        gout[0] = gsigma * nv_exp_clamped(__uint_as_float(q[NV_R_OUT * NT]));
-        const uint64_t relu = (uint64_t)q[NV_R_RELU * NT] | ((uint64_t)q[(NV_R_RELU + 1) * NT] << 32);
-        float x0, x1, x2;
-        const bool inside = nv_normalise(P, s.px, s.py, s.pz, x0, x1, x2);
-        float gx, gy, gz;
-        nv_density_backward<NV_RUN_U, NO_W>(P, inside, x0, x1, x2, relu, gout, col, gx, gy, gz);
-        if (!live) { gx = 0.0f; gy = 0.0f; gz = 0.0f; }
-        gx *= s.bx; gy *= s.by; gz *= s.bz;
-        go0 += gx; go1 += gy; go2 += gz;
-        gdx = __builtin_fmaf(s.z, gx, gdx); gdy = __builtin_fmaf(s.z, gy, gdy); gdz = __builtin_fmaf(s.z, gz, gdz);
+        const nv_sample s = nv_sample_at(R, i, ray);
+        nv_run_sample_bwd<NO_W>(P, R, ray, g, s, live, suffix, col, nullptr, K.save + (size_t)n * R.T + jc, NT, acc);
     }
-    const float a0 = nro_wave_sum(go0), a1 = nro_wave_sum(go1), a2 = nro_wave_sum(go2);
-    const float b0 = nro_wave_sum(gdx), b1 = nro_wave_sum(gdy), b2 = nro_wave_sum(gdz);
-    if (lane == 0) {                                                     // an empty ray: exact zeros
-        grays_o[3ull * n] = a0; grays_o[3ull * n + 1] = a1; grays_o[3ull * n + 2] = a2;
-        grays_d[3ull * n] = b0; grays_d[3ull * n + 1] = b1; grays_d[3ull * n + 2] = b2;
-    }
+    nv_run_write_grads<NO_W>(n, acc, nullptr, grays_o, grays_d);
 }
 
 // ---------------------------------------------------------------------------
 // The resampled run (DESIGN.md §3.5 "Resampled run"; include/ngp_hip.h states the contract): NeRFRenderer.run's upsample_steps > 0 branch
 // (nerf/renderer.py:172-204) with sample_pdf's deterministic branch (:12-46).
 //
-//   k_nav_resample   one 256-thread workgroup per ray: k_nav_run_fwd's coarse pass without the colour net (the weights stay in LDS), the cdf of
+//   k_nav_resample   one 256-thread workgroup per ray: the coarse pass = nv_run_sample_fwd without the colour net (the weights stay in LDS), the cdf of
 //                    w[1 : Nc - 1], one binary search per new sample, two rank searches for the merge; writes the merged depth list z [N, T]
 //   k_sample_pdf     the same device functions on caller-given bins / weights (and uniforms): the piece a host restatement reproduces bit for bit
 //   k_nav_run_fwd<true> / _bwd<true> then run over z (nv_sample_at<true>).
@@ -789,31 +796,21 @@ __global__ __launch_bounds__(NV_BLOCK) void k_nav_resample(nav_params P, nav_run
     float* cdf = nv_smem + 16 + NV_PDF_SCAN_BYTES / sizeof(float);      // [Nc - 1]
     float* znew = cdf + 4096;                                            // [Nf]
     const uint32_t n = blockIdx.x, Nc = R.T, T = Nc + Nf;
-    const float ox = R.rays_o[3ull * n], oy = R.rays_o[3ull * n + 1], oz = R.rays_o[3ull * n + 2];
-    const float dx = R.rays_d[3ull * n], dy = R.rays_d[3ull * n + 1], dz = R.rays_d[3ull * n + 2];
-    const float near = R.nears[n], far = R.fars[n], span = far - near;
+    const nv_ray ray = nv_ray_load(R, n);
+    const float near = ray.near, span = ray.span;
 
-    // ---- the coarse pass: k_nav_run_fwd's loop down to the weight ----
+    // ---- the coarse pass: the run's forward down to the weight ----
     float carry = 1.0f;
+    nv_run_sums unused = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
     for (uint32_t c0 = 0; c0 < Nc; c0 += NV_BLOCK) {
         const uint32_t i = c0 + threadIdx.x;
         const bool live = i < Nc;
-        const nv_sample s = nv_sample_at(R, live ? i : Nc - 1, near, far, ox, oy, oz, dx, dy, dz);
-        float x0, x1, x2;
-        const bool inside = nv_normalise(P, s.px, s.py, s.pz, x0, x1, x2);
-        float out[16];
-        nv_density_forward<NV_RUN_U>(P, inside, x0, x1, x2, col, out);
-        float ex, alpha, keep;
-        nv_alpha(s.znext_minus_z, P.density_scale, expf(out[0]), ex, alpha, keep);
-        if (!live) { alpha = 0.0f; keep = 1.0f; }
-        float total;
-        const float Tr = carry * nv_block_excl_product(keep, lds4, total);
-        const float w = alpha * Tr;
+        const nv_sample s = nv_sample_at(R, live ? i : Nc - 1, ray);
+        const float w = nv_run_sample_fwd<NV_BLOCK, false>(P, ray, s, live, carry, col, lds4, nullptr, 0, 0, unused);
         if (live) {
             wts[i] = w;
             if (wout) wout[(size_t)n * Nc + i] = w;
         }
-        carry *= total;
     }
     __syncthreads();                                                     // the weights are written; the column scratch is free
 

@@ -278,6 +278,54 @@ class _nav_density_vj(torch.autograd.Function):
         return (grad_sigma.detach().reshape(-1, 1) * jac).detach(), None, None
 
 
+def _run_call(device, name, *args):
+    """ngp_<name>(*args, stream) on `device`, timed under `name`"""
+    import ngp_hip as _hip
+    with torch.cuda.device(device), _hip.timed(name):
+        _hip.check(getattr(_hip.lib(), "ngp_" + name)(*args, _hip.stream()), name)
+
+
+def _run_prepare(ctx, rays_o, rays_d, owner, num_steps, bg, saved_bytes, keep=()):
+    """What the forwards of the three run Functions share: contiguous float32 rays, near / far, the host arrays, the three outputs, and the per-sample
+    record the backward consumes (108 B per sample, `saved_bytes`(N, num_steps) of it; not kept when nobody will ask for a gradient).  Leaves on ctx what
+    _run_backward reads, `keep` (tensors the route's entry points hold pointers to) included.  Returns the argument groups the forward entry points
+    take: field = (field, prepared), rays = (rays_o .. N), shape = (num_steps, aabb, bg_color), outputs = (image, depth, weights_sum),
+    kept = (saved, saved_bytes); `out`: the three output tensors."""
+    import ctypes
+    import types
+    import raymarching
+    import ngp_hip as _hip
+    rays_o, rays_d = rays_o.contiguous().float(), rays_d.contiguous().float()
+    N, dev, ren, p = rays_o.shape[0], rays_o.device, owner.renderer, _hip.ptr
+    nears, fars = raymarching.near_far_from_aabb(rays_o, rays_d, ren._aabb(), ren.min_near)
+    aabb = (ctypes.c_float * 6)(*ren._aabb_host())
+    bgc = (ctypes.c_float * 3)(*bg)
+    kw = dict(dtype=torch.float32, device=dev)
+    out = (torch.empty(N, 3, **kw), torch.empty(N, **kw), torch.empty(N, **kw))
+    st, prep = owner.struct()
+    need = any(ctx.needs_input_grad[:2])
+    saved = _hip.workspace(saved_bytes(N, num_steps), dev) if need else None
+    ctx.save_for_backward(rays_o, rays_d, nears, fars, saved if need else torch.empty(0, device=dev), *keep)
+    ctx.owner, ctx.num_steps, ctx.bg, ctx.aabb = owner, num_steps, bgc, aabb
+    return types.SimpleNamespace(device=dev, out=out, field=(ctypes.byref(st), p(prep)), rays=(p(rays_o), p(rays_d), p(nears), p(fars), N), aabb=aabb,
+                                 shape=(num_steps, aabb, bgc), outputs=tuple(p(v) for v in out), kept=(p(saved), saved.numel() if need else 0))
+
+
+def _run_backward(ctx, grads, name, lead=(), trail=()):
+    """What their backwards share: ngp_<name>(field, prepared, *lead, rays .., the three output gradients, saved, grad_rays_o, grad_rays_d, *trail) ->
+    the gradients of forward's inputs (the rays' two; the rest take none)"""
+    import ctypes
+    import ngp_hip as _hip
+    rays_o, rays_d, nears, fars, saved = ctx.saved_tensors[:5]
+    p = _hip.ptr
+    grads = [g.detach().contiguous().float() for g in grads]
+    go, gd = torch.empty_like(rays_o), torch.empty_like(rays_d)
+    st, prep = ctx.owner.struct()
+    _run_call(rays_o.device, name, ctypes.byref(st), p(prep), *lead, p(rays_o), p(rays_d), p(nears), p(fars), rays_o.shape[0], ctx.num_steps, ctx.aabb, ctx.bg,
+              *(p(g) for g in grads), p(saved), saved.numel(), p(go), p(gd), *trail)
+    return (go, gd) + (None,) * (len(ctx.needs_input_grad) - 2)
+
+
 class _nav_run(torch.autograd.Function):
     """NeRFRenderer.run(num_steps, upsample_steps = 0, perturb = False) for [N,3] rays: one launch forward, one backward to the rays.
     Second derivatives (the pose filter's Hessian, nav/estimator_helpers.py:384): in the reference every path from the rays to the image crosses an
@@ -287,47 +335,14 @@ class _nav_run(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, rays_o, rays_d, owner, num_steps, bg):
-        import ctypes
-        import raymarching
         import ngp_hip as _hip
-        rays_o, rays_d = rays_o.contiguous().float(), rays_d.contiguous().float()
-        N = rays_o.shape[0]
-        ren = owner.renderer
-        aabb_t = ren._aabb()
-        nears, fars = raymarching.near_far_from_aabb(rays_o, rays_d, aabb_t, ren.min_near)
-        aabb = (ctypes.c_float * 6)(*ren._aabb_host())
-        bgc = (ctypes.c_float * 3)(*bg)
-        image = torch.empty(N, 3, dtype=torch.float32, device=rays_o.device)
-        depth = torch.empty(N, dtype=torch.float32, device=rays_o.device)
-        ws = torch.empty(N, dtype=torch.float32, device=rays_o.device)
-        st, prep = owner.struct()
-        L = _hip.lib()
-        # the per-sample record the backward consumes (108 B per sample); not kept when nobody will ask for a gradient
-        need = any(ctx.needs_input_grad[:2])
-        saved = _hip.workspace(L.ngp_nav_run_saved_bytes(N, int(num_steps)), rays_o.device) if need else None
-        with torch.cuda.device(rays_o.device), _hip.timed("nav_run_forward"):
-            _hip.check(L.ngp_nav_run_forward(ctypes.byref(st), _hip.ptr(prep), _hip.ptr(rays_o), _hip.ptr(rays_d), _hip.ptr(nears), _hip.ptr(fars),
-                                             N, int(num_steps), aabb, bgc, _hip.ptr(image), _hip.ptr(depth), _hip.ptr(ws),
-                                             _hip.ptr(saved), saved.numel() if need else 0, _hip.stream()), "nav_run_forward")
-        ctx.save_for_backward(rays_o, rays_d, nears, fars, saved if need else torch.empty(0, device=rays_o.device))
-        ctx.owner, ctx.num_steps, ctx.bg, ctx.aabb = owner, int(num_steps), bgc, aabb
-        return image, depth, ws
+        a = _run_prepare(ctx, rays_o, rays_d, owner, int(num_steps), bg, _hip.lib().ngp_nav_run_saved_bytes)
+        _run_call(a.device, "nav_run_forward", *a.field, *a.rays, *a.shape, *a.outputs, *a.kept)
+        return a.out
 
     @staticmethod
     def backward(ctx, g_image, g_depth, g_ws):
-        import ctypes
-        import ngp_hip as _hip
-        rays_o, rays_d, nears, fars, saved = ctx.saved_tensors
-        g_image, g_depth, g_ws = g_image.detach(), g_depth.detach(), g_ws.detach()
-        N = rays_o.shape[0]
-        go, gd = torch.empty_like(rays_o), torch.empty_like(rays_d)
-        st, prep = ctx.owner.struct()
-        with torch.cuda.device(rays_o.device), _hip.timed("nav_run_backward"):
-            _hip.check(_hip.lib().ngp_nav_run_backward(ctypes.byref(st), _hip.ptr(prep), _hip.ptr(rays_o), _hip.ptr(rays_d), _hip.ptr(nears), _hip.ptr(fars),
-                                                       N, ctx.num_steps, ctx.aabb, ctx.bg, _hip.ptr(g_image.contiguous().float()),
-                                                       _hip.ptr(g_depth.contiguous().float()), _hip.ptr(g_ws.contiguous().float()),
-                                                       _hip.ptr(saved), saved.numel(), _hip.ptr(go), _hip.ptr(gd), _hip.stream()), "nav_run_backward")
-        return go, gd, None, None, None
+        return _run_backward(ctx, (g_image, g_depth, g_ws), "nav_run_backward")
 
 
 def occupancy_grid(renderer):
@@ -352,48 +367,19 @@ class _nav_run_occ(torch.autograd.Function):
     @staticmethod
     def forward(ctx, rays_o, rays_d, owner, num_steps, bg, counts=None):
         import ctypes
-        import raymarching
         import ngp_hip as _hip
-        rays_o, rays_d = rays_o.contiguous().float(), rays_d.contiguous().float()
         N = rays_o.shape[0]
-        ren = owner.renderer
-        grid, bits = occupancy_grid(ren)
+        ctx.grid, bits = occupancy_grid(owner.renderer)
         if counts is not None and not (counts.is_cuda and counts.dtype == torch.int32 and counts.is_contiguous() and counts.numel() == N):
             raise ValueError(f"counts must be a contiguous int32 [{N}] tensor on the GPU")
-        nears, fars = raymarching.near_far_from_aabb(rays_o, rays_d, ren._aabb(), ren.min_near)
-        aabb = (ctypes.c_float * 6)(*ren._aabb_host())
-        bgc = (ctypes.c_float * 3)(*bg)
-        image = torch.empty(N, 3, dtype=torch.float32, device=rays_o.device)
-        depth = torch.empty(N, dtype=torch.float32, device=rays_o.device)
-        ws = torch.empty(N, dtype=torch.float32, device=rays_o.device)
-        st, prep = owner.struct()
-        L = _hip.lib()
-        need = any(ctx.needs_input_grad[:2])
-        saved = _hip.workspace(L.ngp_nav_run_occ_saved_bytes(N, int(num_steps)), rays_o.device) if need else None
-        with torch.cuda.device(rays_o.device), _hip.timed("nav_run_occ_forward"):
-            _hip.check(L.ngp_nav_run_occ_forward(ctypes.byref(st), _hip.ptr(prep), ctypes.byref(grid), _hip.ptr(rays_o), _hip.ptr(rays_d), _hip.ptr(nears),
-                                                 _hip.ptr(fars), N, int(num_steps), aabb, bgc, _hip.ptr(image), _hip.ptr(depth), _hip.ptr(ws),
-                                                 _hip.ptr(counts), _hip.ptr(saved), saved.numel() if need else 0, _hip.stream()), "nav_run_occ_forward")
-        ctx.save_for_backward(rays_o, rays_d, nears, fars, saved if need else torch.empty(0, device=rays_o.device), bits)
-        ctx.owner, ctx.num_steps, ctx.bg, ctx.aabb, ctx.grid = owner, int(num_steps), bgc, aabb, grid
-        return image, depth, ws
+        a = _run_prepare(ctx, rays_o, rays_d, owner, int(num_steps), bg, _hip.lib().ngp_nav_run_occ_saved_bytes, keep=(bits,))
+        _run_call(a.device, "nav_run_occ_forward", *a.field, ctypes.byref(ctx.grid), *a.rays, *a.shape, *a.outputs, _hip.ptr(counts), *a.kept)
+        return a.out
 
     @staticmethod
     def backward(ctx, g_image, g_depth, g_ws):
         import ctypes
-        import ngp_hip as _hip
-        rays_o, rays_d, nears, fars, saved, _bits = ctx.saved_tensors
-        g_image, g_depth, g_ws = g_image.detach(), g_depth.detach(), g_ws.detach()
-        N = rays_o.shape[0]
-        go, gd = torch.empty_like(rays_o), torch.empty_like(rays_d)
-        st, prep = ctx.owner.struct()
-        with torch.cuda.device(rays_o.device), _hip.timed("nav_run_occ_backward"):
-            _hip.check(_hip.lib().ngp_nav_run_occ_backward(ctypes.byref(st), _hip.ptr(prep), ctypes.byref(ctx.grid), _hip.ptr(rays_o), _hip.ptr(rays_d),
-                                                           _hip.ptr(nears), _hip.ptr(fars), N, ctx.num_steps, ctx.aabb, ctx.bg,
-                                                           _hip.ptr(g_image.contiguous().float()), _hip.ptr(g_depth.contiguous().float()),
-                                                           _hip.ptr(g_ws.contiguous().float()), _hip.ptr(saved), saved.numel(), _hip.ptr(go), _hip.ptr(gd),
-                                                           _hip.stream()), "nav_run_occ_backward")
-        return go, gd, None, None, None, None
+        return _run_backward(ctx, (g_image, g_depth, g_ws), "nav_run_occ_backward", lead=(ctypes.byref(ctx.grid),))
 
 
 class _nav_run_resampled(torch.autograd.Function):
@@ -404,51 +390,19 @@ class _nav_run_resampled(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, rays_o, rays_d, owner, num_steps, upsample_steps, bg):
-        import ctypes
-        import raymarching
         import ngp_hip as _hip
-        rays_o, rays_d = rays_o.contiguous().float(), rays_d.contiguous().float()
-        N, Nc, Nf = rays_o.shape[0], int(num_steps), int(upsample_steps)
-        T = Nc + Nf
-        ren = owner.renderer
-        nears, fars = raymarching.near_far_from_aabb(rays_o, rays_d, ren._aabb(), ren.min_near)
-        aabb = (ctypes.c_float * 6)(*ren._aabb_host())
-        bgc = (ctypes.c_float * 3)(*bg)
-        kw = dict(dtype=torch.float32, device=rays_o.device)
-        image, depth, ws = torch.empty(N, 3, **kw), torch.empty(N, **kw), torch.empty(N, **kw)
-        z = torch.empty(N, max(T, 1), **kw)
-        st, prep = owner.struct()
-        L = _hip.lib()
-        need = any(ctx.needs_input_grad[:2])
-        with torch.cuda.device(rays_o.device):
-            with _hip.timed("nav_run_resample"):
-                _hip.check(L.ngp_nav_run_resample(ctypes.byref(st), _hip.ptr(prep), _hip.ptr(rays_o), _hip.ptr(rays_d), _hip.ptr(nears), _hip.ptr(fars),
-                                                  N, Nc, Nf, aabb, _hip.ptr(z), None, _hip.stream()), "nav_run_resample")
-            saved = _hip.workspace(L.ngp_nav_run_saved_bytes(N, T), rays_o.device) if need else None
-            with _hip.timed("nav_run_at_forward"):
-                _hip.check(L.ngp_nav_run_at_forward(ctypes.byref(st), _hip.ptr(prep), _hip.ptr(rays_o), _hip.ptr(rays_d), _hip.ptr(nears), _hip.ptr(fars),
-                                                    N, T, aabb, bgc, _hip.ptr(image), _hip.ptr(depth), _hip.ptr(ws), _hip.ptr(saved),
-                                                    saved.numel() if need else 0, _hip.ptr(z), Nc, _hip.stream()), "nav_run_at_forward")
-        ctx.save_for_backward(rays_o, rays_d, nears, fars, saved if need else torch.empty(0, device=rays_o.device), z)
-        ctx.owner, ctx.steps, ctx.bg, ctx.aabb = owner, (Nc, T), bgc, aabb
-        return image, depth, ws
+        Nc, Nf = int(num_steps), int(upsample_steps)
+        z = torch.empty(rays_o.shape[0], max(Nc + Nf, 1), dtype=torch.float32, device=rays_o.device)
+        a = _run_prepare(ctx, rays_o, rays_d, owner, Nc + Nf, bg, _hip.lib().ngp_nav_run_saved_bytes, keep=(z,))
+        ctx.coarse_steps = Nc
+        _run_call(a.device, "nav_run_resample", *a.field, *a.rays, Nc, Nf, a.aabb, _hip.ptr(z), None)
+        _run_call(a.device, "nav_run_at_forward", *a.field, *a.rays, *a.shape, *a.outputs, *a.kept, _hip.ptr(z), Nc)
+        return a.out
 
     @staticmethod
     def backward(ctx, g_image, g_depth, g_ws):
-        import ctypes
         import ngp_hip as _hip
-        rays_o, rays_d, nears, fars, saved, z = ctx.saved_tensors
-        g_image, g_depth, g_ws = g_image.detach(), g_depth.detach(), g_ws.detach()
-        N = rays_o.shape[0]
-        Nc, T = ctx.steps
-        go, gd = torch.empty_like(rays_o), torch.empty_like(rays_d)
-        st, prep = ctx.owner.struct()
-        with torch.cuda.device(rays_o.device), _hip.timed("nav_run_at_backward"):
-            _hip.check(_hip.lib().ngp_nav_run_at_backward(ctypes.byref(st), _hip.ptr(prep), _hip.ptr(rays_o), _hip.ptr(rays_d), _hip.ptr(nears),
-                                                          _hip.ptr(fars), N, T, ctx.aabb, ctx.bg, _hip.ptr(g_image.contiguous().float()),
-                                                          _hip.ptr(g_depth.contiguous().float()), _hip.ptr(g_ws.contiguous().float()), _hip.ptr(saved),
-                                                          saved.numel(), _hip.ptr(go), _hip.ptr(gd), _hip.ptr(z), Nc, _hip.stream()), "nav_run_at_backward")
-        return go, gd, None, None, None, None
+        return _run_backward(ctx, (g_image, g_depth, g_ws), "nav_run_at_backward", trail=(_hip.ptr(ctx.saved_tensors[5]), ctx.coarse_steps))
 
 
 class NativeNavQueries(NavQueries):
@@ -486,17 +440,21 @@ class NativeNavQueries(NavQueries):
         pts = x.reshape(-1, 3) @ self._rot_on(x.device)
         return _nav_density.apply(pts, self.native).reshape(x.shape[:-1])
 
-    def render_fn(self, rays_o, rays_d):
-        """rays [B, N, 3] -> {'image' [B,N,3], 'depth' [B,N]} like NeRFRenderer.render(staged=True, bg_color=1, perturb=False)"""
+    def _render_chunks(self, rays_o, rays_d, run):
+        """rays [B, N, 3] through run(rays_o [n,3], rays_d [n,3]) -> (image, depth, weights_sum), max_ray_batch rays at a time"""
         B, N = rays_o.shape[:2]
         images, depths = [], []
         for b in range(B):
             for head in range(0, N, self.max_ray_batch):
                 tail = min(head + self.max_ray_batch, N)
-                img, dep, _ = _nav_run.apply(rays_o[b, head:tail], rays_d[b, head:tail], self.native, self.num_steps, (1.0, 1.0, 1.0))
+                img, dep, _ = run(rays_o[b, head:tail], rays_d[b, head:tail])
                 images.append(img)
                 depths.append(dep)
         return {"image": torch.cat(images).view(B, N, 3), "depth": torch.cat(depths).view(B, N)}
+
+    def render_fn(self, rays_o, rays_d):
+        """rays [B, N, 3] -> {'image' [B,N,3], 'depth' [B,N]} like NeRFRenderer.render(staged=True, bg_color=1, perturb=False)"""
+        return self._render_chunks(rays_o, rays_d, lambda o, d: _nav_run.apply(o, d, self.native, self.num_steps, (1.0, 1.0, 1.0)))
 
     def render_fn_resampled(self, rays_o, rays_d, upsample_steps, num_steps=None):
         """render_fn with NeRFRenderer.run's importance resampling (DESIGN 3.5 "Resampled run"): num_steps (default: the queries') coarse samples per ray,
@@ -506,15 +464,7 @@ class NativeNavQueries(NavQueries):
         Nf = int(upsample_steps)
         if Nc < 3 or Nf < 1 or Nc + Nf > 4096:
             raise ValueError(f"render_fn_resampled needs num_steps >= 3, upsample_steps >= 1 and at most 4096 samples per ray, got {Nc} + {Nf}")
-        B, N = rays_o.shape[:2]
-        images, depths = [], []
-        for b in range(B):
-            for head in range(0, N, self.max_ray_batch):
-                tail = min(head + self.max_ray_batch, N)
-                img, dep, _ = _nav_run_resampled.apply(rays_o[b, head:tail], rays_d[b, head:tail], self.native, Nc, Nf, (1.0, 1.0, 1.0))
-                images.append(img)
-                depths.append(dep)
-        return {"image": torch.cat(images).view(B, N, 3), "depth": torch.cat(depths).view(B, N)}
+        return self._render_chunks(rays_o, rays_d, lambda o, d: _nav_run_resampled.apply(o, d, self.native, Nc, Nf, (1.0, 1.0, 1.0)))
 
     def render_fn_occupied(self, rays_o, rays_d, counts=None):
         """rays [N,3] -> (image [N,3], depth [N], weights_sum [N]) of the run with the renderer's occupancy grid consulted: the sigma of every lattice sample

@@ -64,8 +64,9 @@ def bg3(case):
     return tuple(float(v) for v in (case["bg"] if not np.isscalar(case["bg"]) else (case["bg"],) * 3))
 
 
-def gpu_run(dev, case, bits, rows=None):
-    """the case through ngp.nav._nav_run_occ (one launch forward, one backward) -> numpy dict like _run_occ_cases.masked_run's, plus counts"""
+def gpu_run(dev, case, bits, rows=None, dense=False):
+    """the case through ngp.nav._nav_run_occ (one launch forward, one backward) -> numpy dict like _run_occ_cases.masked_run's, plus counts.
+    dense: through ngp.nav._nav_run on the same renderer instead (the counts stay as they were filled)"""
     from ngp import nav
     o, d, _ = C.case_rays(case)
     G, Gd, Gw = C.loss_weights(o.shape[0])
@@ -74,7 +75,10 @@ def gpu_run(dev, case, bits, rows=None):
     _, native = rig(dev, case, bits)
     ro, rd = t(o, dev).requires_grad_(True), t(d, dev).requires_grad_(True)
     counts = torch.full((o.shape[0],), -7, dtype=torch.int32, device=dev)
-    image, depth, ws = nav._nav_run_occ.apply(ro, rd, native, case["T"], bg3(case), counts)
+    if dense:
+        image, depth, ws = nav._nav_run.apply(ro, rd, native, case["T"], bg3(case))
+    else:
+        image, depth, ws = nav._nav_run_occ.apply(ro, rd, native, case["T"], bg3(case), counts)
     loss = 0
     if "image" in case["terms"]:
         loss = loss + (image * t(G, dev)).sum()
@@ -143,6 +147,20 @@ def test_full_grid_against_the_dense_pinned_reference(dev, name):
     got = gpu_run(dev, case, RO.bitfield("ones", case["bound"]))
     worst = check(f"{name} dense reference", got, r)
     print(f"{name} against run_reference: worst ratios " + " ".join(f"{k} {v:.2f}" for k, v in worst.items()))
+
+
+@pytest.mark.parametrize("T", [1, 3, 63, 64])
+def test_full_grid_and_one_chunk_is_the_dense_run_bit_for_bit(dev, T):
+    """Every cell occupied and T <= 64: the compacted list is the lattice and fits one chunk, so the one-wave kernels and the four-wave kernels run the
+    one per-sample body (nv_run_sample_fwd / _bwd of csrc/nav_field.hip) on the same numbers.  In the dense kernels only wave 0 holds live samples; the
+    other waves hand the team scans exact 1.0f factors and +0.0f terms, and a lane's sums start at +0, so no rounding and no sign of zero differs."""
+    case = C._run_case(field="contrast", T=T, count=16)
+    bits = RO.bitfield("ones", case["bound"])
+    occ, dense = gpu_run(dev, case, bits), gpu_run(dev, case, bits, dense=True)
+    assert np.all(occ["counts"] == T)
+    for k in ("image", "depth", "weights_sum", "grad_o", "grad_d"):
+        assert np.array_equal(occ[k].view(np.uint32), dense[k].view(np.uint32)), (k, np.flatnonzero((occ[k] != dense[k]).reshape(16, -1).any(axis=1)))
+    assert T < 63 or (np.abs(occ["grad_d"]).sum() > 0 and occ["weights_sum"].max() > 0.5)      # the rays do hit something
 
 
 # ------------------------------------------------------------------------------------------------------------------------
